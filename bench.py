@@ -12,6 +12,11 @@ Weak scaling: each rank round-trips its own R rows.
 
 Contract (driver): rank 0 prints exactly one JSON line; timing brackets are
 barrier + torch.cuda.synchronize on both sides; MAX elapsed over ranks.
+
+A plain run sets up, warms up, times --steps steps and prints the line.
+--full adds the round-trip correctness probe before timing; --dump-outputs
+DIR saves what the last timed step produced (seeded inputs, so two builds
+can be compared array for array).
 """
 
 import argparse
@@ -63,6 +68,46 @@ def make_batch(rows: int, seed: int):
     return RecordBatch(schema, [id_col, ints, floats, tokens], R)
 
 
+_DUMP_BUDGET = 30 << 20  # bytes over all arrays; twice that if every one of
+#                          them splits in two (hard limit: 64 MB in all)
+_DUMP_SEED = 20260920
+
+
+def dump_outputs(out_dir: str, batch, fpath: str):
+    """Write what one step produced as <name>.npy (float32/float64): every
+    array of the decoded host batch plus the bytes of the file it wrote.
+    An array larger than its share of the budget is cut down to a fixed,
+    seeded sample of its elements (same indices for the same shapes), so two
+    builds can be compared file for file."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    for f, c in zip(batch.schema.fields, batch.columns):
+        for part in ("presence", "row_off", "values", "elem_off", "list_off",
+                     "sub_off"):
+            a = getattr(c, part)
+            if a is not None:
+                arrays[f"{f.name}.{part}"] = np.asarray(a).reshape(-1)
+    arrays["file_image"] = np.memmap(fpath, np.uint8, "r")
+
+    cap = _DUMP_BUDGET // len(arrays)
+    for k, (name, a) in enumerate(arrays.items()):
+        wide = a.dtype.itemsize >= 8
+        keep = cap // (8 if wide else 4)
+        if a.size > keep:
+            rng = np.random.default_rng(_DUMP_SEED + k)
+            a = a[np.sort(rng.choice(a.size, keep, replace=False))]
+        if a.dtype.kind in "iu" and wide and a.size and \
+                max(int(a.max()), -int(a.min())) > 2**53:
+            # float64 holds 53 bits: keep such integers exact as two words
+            np.save(os.path.join(out_dir, f"{name}.hi32.npy"),
+                    (a >> 32).astype(np.float64))
+            np.save(os.path.join(out_dir, f"{name}.lo32.npy"),
+                    (a & 0xFFFFFFFF).astype(np.float64))
+        else:
+            np.save(os.path.join(out_dir, f"{name}.npy"),
+                    a.astype(np.float64 if wide else np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -74,7 +119,16 @@ def main():
     ap.add_argument("--engine", type=str, default="auto")
     ap.add_argument("--phases", action="store_true",
                     help="print per-phase timing breakdown (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the round-trip against the input "
+                         "before timing (a plain run only times)")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write the last step's "
+                         "decoded columns and file bytes as DIR/<name>.npy "
+                         "(rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
 
@@ -140,15 +194,16 @@ def main():
             return cpu_engine.decode_buffer(data, batch.schema, "Example")
         engine_name = "cpu"
 
-    # one correctness probe before timing: decoded ids must match
+    # one untimed step creates the file (its size goes into the result line);
+    # --full uses it as a correctness probe too: decoded ids must match
     out = step()
-    if engine_name == "gpu":
-        from spark_tfrecord_amd.engine import gpu as gpu_engine
-        got = out.columns[0].values.cpu().numpy()
-    else:
-        got = np.asarray(out.columns[0].values)
-    assert np.array_equal(got, np.asarray(batch.columns[0].values)), \
-        "round-trip mismatch"
+    if args.full:
+        if engine_name == "gpu":
+            got = out.columns[0].values.cpu().numpy()
+        else:
+            got = np.asarray(out.columns[0].values)
+        assert np.array_equal(got, np.asarray(batch.columns[0].values)), \
+            "round-trip mismatch"
     file_bytes = os.path.getsize(fpath)
 
     def sync():
@@ -164,7 +219,8 @@ def main():
         phase_t.clear()  # report timed steps only (drop warmup one-offs)
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = None  # drop the previous step's columns before the next run
+        out = step()
     sync()
     elapsed = time.perf_counter() - t0
 
@@ -184,6 +240,11 @@ def main():
                      for k, v in phase_t.items()}
         print(f"# phase breakdown (per timed step): {breakdown}",
               file=sys.stderr)
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs,
+                     gpu_engine.batch_to_host(out) if engine_name == "gpu"
+                     else out, fpath)
 
     if rank == 0:
         print(json.dumps({

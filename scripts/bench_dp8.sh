@@ -30,7 +30,7 @@ run_n () {  # run_n <nproc> <cmd...>
 for N in 1 2 4 8; do
   [ "$N" -gt "$NGPU" ] && break
   echo "=== dp$N flagship (bench.py) ==="
-  run_n "$N" bench.py --gpus "$N" --steps 10 --warmup 3 --rows "$ROWS" \
+  run_n "$N" bench.py --gpus "$N" --steps 10 --warmup 3 --rows "$ROWS" --full \
     | tee "$OUT_DIR/dp${N}_flagship.json"
   for CFG in partitionby infer gzip_bytearray; do
     echo "=== dp$N $CFG ==="
