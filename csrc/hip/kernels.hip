@@ -107,7 +107,8 @@ __global__ void scan_records_kernel(const u8* __restrict__ data,
                                     const u8* __restrict__ schema_blob, int F,
                                     FieldStat* __restrict__ stats,
                                     int32_t* __restrict__ err,
-                                    unsigned long long* crc_err) {
+                                    unsigned long long* crc_err,
+                                    i64 rec_base) {
   __shared__ uint32_t tab[8][256];
   if (crc_err) stage_crc_tables(tab);
   SchemaView schema = schema_view(schema_blob);
@@ -135,13 +136,13 @@ __global__ void scan_records_kernel(const u8* __restrict__ data,
       __builtin_memcpy(&data_crc, h + 12 + len[r], 4);
       bool ok = mask_crc(crc32c_sw(h, 8, 0, tab)) == len_crc &&
                 mask_crc(payload_crc) == data_crc;
-      if (!ok) atomicMin(crc_err, (unsigned long long)(r + 1));
+      if (!ok) atomicMin(crc_err, (unsigned long long)(rec_base + r + 1));
     } else {
       rc = scan_record(data, off[r], len[r], fmt, schema, st);
     }
-    if (rc != ERR_OK) set_err(err, rc, r);
+    if (rc != ERR_OK) set_err(err, rc, rec_base + r);
     for (int f = 0; f < F; ++f)
-      if (st[f].err != ERR_OK) set_err(err, st[f].err, r);
+      if (st[f].err != ERR_OK) set_err(err, st[f].err, rec_base + r);
   }
 }
 
@@ -164,15 +165,18 @@ struct DevFieldDst {
   const i64* list_base;  // [R+1] exclusive scan of nlists
 };
 
+// Covers records [r0, r0 + R); stats and the base planes are indexed by the
+// absolute record number.
 __global__ void extract_fields_kernel(const u8* __restrict__ data, i64 R, int F,
                                       const FieldStat* __restrict__ stats,
                                       const DevFieldDst* __restrict__ metas,
-                                      int32_t* __restrict__ err) {
+                                      int32_t* __restrict__ err, i64 r0) {
   i64 total = R * F;
   for (i64 idx = blockIdx.x * (i64)blockDim.x + threadIdx.x; idx < total;
        idx += (i64)gridDim.x * blockDim.x) {
-    i64 r = idx / F;
-    int f = (int)(idx - r * F);
+    i64 q = idx / F;
+    int f = (int)(idx - q * F);
+    i64 r = r0 + q;
     const DevFieldDst& m = metas[f];
     const FieldStat& st = stats[r * F + f];
     DecodeDst dst{m.i64_vals, m.f32_vals, m.bytes_data, m.elem_len, m.sub_count};
@@ -538,7 +542,8 @@ __global__ void scan_records_wave_kernel(const u8* __restrict__ data,
                                          const u8* __restrict__ schema_blob,
                                          int F, FieldStat* __restrict__ stats,
                                          int32_t* __restrict__ err,
-                                         unsigned long long* crc_err) {
+                                         unsigned long long* crc_err,
+                                         i64 rec_base) {
   __shared__ uint32_t tab[8][256];
   stage_crc_tables(tab);
   SchemaView schema = schema_view(schema_blob);
@@ -550,9 +555,9 @@ __global__ void scan_records_wave_kernel(const u8* __restrict__ data,
       FieldStat* st = stats + r * F;
       for (int f = 0; f < F; ++f) field_stat_clear(&st[f]);
       int32_t rc = scan_record(data, off[r], len[r], fmt, schema, st);
-      if (rc != ERR_OK) set_err(err, rc, r);
+      if (rc != ERR_OK) set_err(err, rc, rec_base + r);
       for (int f = 0; f < F; ++f)
-        if (st[f].err != ERR_OK) set_err(err, st[f].err, r);
+        if (st[f].err != ERR_OK) set_err(err, st[f].err, rec_base + r);
     }
     if (crc_err) {
       const u8* h = data + off[r] - 12;
@@ -563,7 +568,7 @@ __global__ void scan_records_wave_kernel(const u8* __restrict__ data,
         __builtin_memcpy(&data_crc, h + 12 + len[r], 4);
         bool ok = mask_crc(crc32c_sw(h, 8, 0, tab)) == len_crc &&
                   mask_crc(payload) == data_crc;
-        if (!ok) atomicMin(crc_err, (unsigned long long)(r + 1));
+        if (!ok) atomicMin(crc_err, (unsigned long long)(rec_base + r + 1));
       }
     }
   }
@@ -574,13 +579,14 @@ __global__ void extract_fields_wave_kernel(const u8* __restrict__ data, i64 R,
                                            int F,
                                            const FieldStat* __restrict__ stats,
                                            const DevFieldDst* __restrict__ metas,
-                                           int32_t* __restrict__ err) {
+                                           int32_t* __restrict__ err, i64 r0) {
   i64 total = R * F;
   i64 wave = (blockIdx.x * (i64)blockDim.x + threadIdx.x) / 64;
   i64 nwaves = ((i64)gridDim.x * blockDim.x) / 64;
   for (i64 idx = wave; idx < total; idx += nwaves) {
-    i64 r = idx / F;
-    int f = (int)(idx - r * F);
+    i64 q = idx / F;
+    int f = (int)(idx - q * F);
+    i64 r = r0 + q;
     const DevFieldDst& m = metas[f];
     const FieldStat& st = stats[r * F + f];
     DecodeDst dst{m.i64_vals, m.f32_vals, m.bytes_data, m.elem_len, m.sub_count};
@@ -935,6 +941,29 @@ __global__ void frame_scan_pass_kernel(const u8* __restrict__ data, i64 N,
                      });
 }
 
+// Frame-chain check over candidates [0, C) of one arrived slice: candidate k
+// must start where candidate k-1 ended (pos[k-1] + 16 + len[k-1]); the first
+// one must start at *carry_in, the end of the previous slice's last
+// candidate (0 for the first slice). Writes off[k] = pos[k] + 12, the end
+// of the last candidate to *carry_out and raises *broken on any mismatch.
+// carry_in and carry_out are distinct words, so no launch reads a value it
+// also writes.
+__global__ void frame_chain_kernel(const i64* __restrict__ pos,
+                                   const i64* __restrict__ len, i64 C,
+                                   const i64* __restrict__ carry_in,
+                                   i64* __restrict__ carry_out,
+                                   i64* __restrict__ off,
+                                   i64* __restrict__ broken) {
+  for (i64 k = blockIdx.x * (i64)blockDim.x + threadIdx.x; k < C;
+       k += (i64)gridDim.x * blockDim.x) {
+    i64 p = pos[k];
+    i64 want = k == 0 ? *carry_in : pos[k - 1] + 16 + len[k - 1];
+    if (p != want) *broken = 1;
+    off[k] = p + 12;
+    if (k == C - 1) *carry_out = p + 16 + len[k];
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Schema inference on device ("per-GPU type-lattice histogram
 // kernel + RCCL all-reduce"). One record per lane walks the Features /
@@ -1202,10 +1231,13 @@ __global__ void gather_payloads_kernel(const u8* __restrict__ data,
 // torch current stream so the kernels interleave with cumsum/casts).
 // ---------------------------------------------------------------------------
 
-inline int grid_for(i64 n) {
+// max_blocks > 0 lowers the cap: the kernels are grid-stride, so a smaller
+// grid only leaves CUs free for work on other streams (the copy blits).
+inline int grid_for(i64 n, i64 max_blocks = 0) {
   // ≫256 workgroups to fill 8 XCDs × 32 CUs; cap so grid-stride amortizes.
   i64 blocks = (n + kBlock - 1) / kBlock;
-  if (blocks > 8192) blocks = 8192;
+  i64 cap = max_blocks > 0 && max_blocks < 8192 ? max_blocks : 8192;
+  if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
   return (int)blocks;
 }
@@ -1225,29 +1257,36 @@ void gpu_crc_verify(uintptr_t data, uintptr_t off, uintptr_t len, i64 R,
   HIP_CHECK(hipGetLastError());
 }
 
+// off/len/stats point at the launch's first record; rec_base is that
+// record's absolute index, so err[1] and crc_err carry absolute indices and
+// one pair of error buffers serves every launch over a file.
 void gpu_scan_records(uintptr_t data, uintptr_t off, uintptr_t len, i64 R,
                       int32_t fmt, uintptr_t schema_blob, int F, uintptr_t stats,
                       uintptr_t err, uintptr_t crc_err, uintptr_t stream,
-                      i64 avg_bytes) {
+                      i64 avg_bytes, i64 rec_base, i64 max_blocks) {
+  if (R <= 0) return;
   if (avg_bytes > kWaveRecordBytes) {  // few big records: one per wave
-    hipLaunchKernelGGL(scan_records_wave_kernel, dim3(grid_for(R * 64)),
-                       dim3(kBlock), 0, (hipStream_t)stream, (const u8*)data,
-                       (const i64*)off, (const i64*)len, R, fmt,
-                       (const u8*)schema_blob, F, (FieldStat*)stats,
-                       (int32_t*)err, (unsigned long long*)crc_err);
-  } else {
-    hipLaunchKernelGGL(scan_records_kernel, dim3(grid_for(R)), dim3(kBlock), 0,
+    hipLaunchKernelGGL(scan_records_wave_kernel,
+                       dim3(grid_for(R * 64, max_blocks)), dim3(kBlock), 0,
                        (hipStream_t)stream, (const u8*)data, (const i64*)off,
                        (const i64*)len, R, fmt, (const u8*)schema_blob, F,
                        (FieldStat*)stats, (int32_t*)err,
-                       (unsigned long long*)crc_err);
+                       (unsigned long long*)crc_err, rec_base);
+  } else {
+    hipLaunchKernelGGL(scan_records_kernel, dim3(grid_for(R, max_blocks)),
+                       dim3(kBlock), 0, (hipStream_t)stream, (const u8*)data,
+                       (const i64*)off, (const i64*)len, R, fmt,
+                       (const u8*)schema_blob, F, (FieldStat*)stats,
+                       (int32_t*)err, (unsigned long long*)crc_err, rec_base);
   }
   HIP_CHECK(hipGetLastError());
 }
 
 void gpu_extract_fields(uintptr_t data, i64 R, int F, uintptr_t stats,
                         py::list metas, uintptr_t meta_dev, uintptr_t err,
-                        uintptr_t stream, i64 avg_bytes) {
+                        uintptr_t stream, i64 avg_bytes, i64 r0,
+                        i64 max_blocks) {
+  if (R <= 0 || F <= 0) return;
   std::vector<DevFieldDst> host_metas(F);
   for (int f = 0; f < F; ++f) {
     py::dict d = metas[f].cast<py::dict>();
@@ -1267,15 +1306,17 @@ void gpu_extract_fields(uintptr_t data, i64 R, int F, uintptr_t stats,
                            sizeof(DevFieldDst) * F, hipMemcpyHostToDevice,
                            (hipStream_t)stream));
   if (avg_bytes > kWaveRecordBytes) {
-    hipLaunchKernelGGL(extract_fields_wave_kernel, dim3(grid_for(R * F * 64)),
-                       dim3(kBlock), 0, (hipStream_t)stream, (const u8*)data,
-                       R, F, (const FieldStat*)stats,
-                       (const DevFieldDst*)meta_dev, (int32_t*)err);
+    hipLaunchKernelGGL(extract_fields_wave_kernel,
+                       dim3(grid_for(R * F * 64, max_blocks)), dim3(kBlock), 0,
+                       (hipStream_t)stream, (const u8*)data, R, F,
+                       (const FieldStat*)stats, (const DevFieldDst*)meta_dev,
+                       (int32_t*)err, r0);
   } else {
-    hipLaunchKernelGGL(extract_fields_kernel, dim3(grid_for(R * F)),
-                       dim3(kBlock), 0, (hipStream_t)stream, (const u8*)data,
-                       R, F, (const FieldStat*)stats,
-                       (const DevFieldDst*)meta_dev, (int32_t*)err);
+    hipLaunchKernelGGL(extract_fields_kernel,
+                       dim3(grid_for(R * F, max_blocks)), dim3(kBlock), 0,
+                       (hipStream_t)stream, (const u8*)data, R, F,
+                       (const FieldStat*)stats, (const DevFieldDst*)meta_dev,
+                       (int32_t*)err, r0);
   }
   HIP_CHECK(hipGetLastError());
 }
@@ -1384,6 +1425,17 @@ void gpu_frame_scan_emit(uintptr_t data, i64 N, i64 pos_start, i64 pos_end,
   HIP_CHECK(hipGetLastError());
 }
 
+void gpu_frame_chain(uintptr_t pos, uintptr_t len, i64 C, uintptr_t carry_in,
+                     uintptr_t carry_out, uintptr_t off, uintptr_t broken,
+                     uintptr_t stream) {
+  if (C <= 0) return;
+  hipLaunchKernelGGL(frame_chain_kernel, dim3(grid_for(C)), dim3(kBlock), 0,
+                     (hipStream_t)stream, (const i64*)pos, (const i64*)len, C,
+                     (const i64*)carry_in, (i64*)carry_out, (i64*)off,
+                     (i64*)broken);
+  HIP_CHECK(hipGetLastError());
+}
+
 void gpu_infer_codes(uintptr_t data, uintptr_t off, uintptr_t len, i64 R,
                      int32_t fmt, uintptr_t table, int nslots, uintptr_t err,
                      uintptr_t stream) {
@@ -1455,20 +1507,30 @@ struct Seg3Combine {
   }
 };
 
+// Rows [r0, r0 + n) of every field. The head element of a field's segment
+// adds the running totals already stored at plane[f][r0]: zero at r0 == 0
+// (pre-zeroed by the caller), the previous range's last output otherwise.
 struct Seg3Load {
   const i64* stats;  // [R][F][6]
-  i64 R;
+  i64 n;
   int F;
+  i64 r0;
+  i64 stride;  // plane row stride
+  const i64* b0;
+  const i64* b1;
+  const i64* b2;
   __host__ __device__ Seg3 operator()(i64 idx) const {
-    i64 f = idx / R;
-    i64 r = idx - f * R;
-    const i64* st = stats + (r * F + f) * 6;
-    return Seg3{st[2], st[3], st[4], r == 0 ? 1u : 0u};
+    i64 f = idx / n;
+    i64 q = idx - f * n;
+    const i64* st = stats + ((r0 + q) * F + f) * 6;
+    if (q != 0) return Seg3{st[2], st[3], st[4], 0u};
+    i64 at = f * stride + r0;
+    return Seg3{st[2] + b0[at], st[3] + b1[at], st[4] + b2[at], 1u};
   }
 };
 
 // Writable proxy iterator: element idx scatters (v0,v1,v2) into the three
-// output planes at [f][r+1] (out[f][0] is pre-zeroed by the caller).
+// output planes at [f][r0+q+1] (out[f][0] is pre-zeroed by the caller).
 struct Seg3OutRef {
   i64* o0;
   i64* o1;
@@ -1489,19 +1551,21 @@ struct Seg3OutIt {
   using iterator_category = std::random_access_iterator_tag;
   i64* b0;
   i64* b1;
-  i64* b2;  // [F][R+1] planes
-  i64 R;
+  i64* b2;  // [F][stride] planes
+  i64 n;
+  i64 r0;
+  i64 stride;
   i64 pos;
   __host__ __device__ Seg3OutRef operator*() const { return (*this)[0]; }
   __host__ __device__ Seg3OutRef operator[](i64 k) const {
     i64 idx = pos + k;
-    i64 f = idx / R;
-    i64 r = idx - f * R;
-    i64 at = f * (R + 1) + r + 1;
+    i64 f = idx / n;
+    i64 q = idx - f * n;
+    i64 at = f * stride + r0 + q + 1;
     return Seg3OutRef{b0 + at, b1 + at, b2 + at};
   }
   __host__ __device__ Seg3OutIt operator+(i64 k) const {
-    return Seg3OutIt{b0, b1, b2, R, pos + k};
+    return Seg3OutIt{b0, b1, b2, n, r0, stride, pos + k};
   }
   __host__ __device__ Seg3OutIt& operator+=(i64 k) {
     pos += k;
@@ -1516,25 +1580,37 @@ struct Seg3OutIt {
 size_t gpu_stat_scan_temp_bytes(i64 R, int F) {
   size_t bytes = 0;
   auto in = rocprim::make_transform_iterator(
-      rocprim::make_counting_iterator<i64>(0), Seg3Load{nullptr, R, F});
-  Seg3OutIt out{nullptr, nullptr, nullptr, R, 0};
+      rocprim::make_counting_iterator<i64>(0),
+      Seg3Load{nullptr, R, F, 0, R + 1, nullptr, nullptr, nullptr});
+  Seg3OutIt out{nullptr, nullptr, nullptr, R, 0, R + 1, 0};
   (void)rocprim::inclusive_scan(nullptr, bytes, in, out, (size_t)(R * F),
                                 Seg3Combine());
   return bytes;
 }
 
+// Scans rows [r0, r1) of stats[R][F] (r1 < 0: to R) into planes whose row
+// stride is `stride` words (0: R + 1). temp must hold
+// gpu_stat_scan_temp_bytes(r1 - r0, F).
 void gpu_stat_scans(uintptr_t temp, size_t temp_bytes, uintptr_t stats, i64 R,
                     int F, uintptr_t val_base, uintptr_t byte_base,
-                    uintptr_t list_base, uintptr_t stream) {
+                    uintptr_t list_base, uintptr_t stream, i64 r0, i64 r1,
+                    i64 stride) {
   auto s = (hipStream_t)stream;
-  if (R <= 0 || F <= 0) return;
+  if (r1 < 0) r1 = R;
+  if (stride <= 0) stride = R + 1;
+  if (r0 < 0 || r1 > R || r1 >= stride)
+    throw std::runtime_error("gpu_stat_scans: range outside the planes");
+  i64 n = r1 - r0;
+  if (n <= 0 || F <= 0) return;
   auto in = rocprim::make_transform_iterator(
       rocprim::make_counting_iterator<i64>(0),
-      Seg3Load{(const i64*)stats, R, F});
-  Seg3OutIt out{(i64*)val_base, (i64*)byte_base, (i64*)list_base, R, 0};
+      Seg3Load{(const i64*)stats, n, F, r0, stride, (const i64*)val_base,
+               (const i64*)byte_base, (const i64*)list_base});
+  Seg3OutIt out{(i64*)val_base, (i64*)byte_base, (i64*)list_base, n, r0,
+                stride, 0};
   size_t tb = temp_bytes;
   HIP_CHECK(rocprim::inclusive_scan((void*)temp, tb, in, out,
-                                    (size_t)(R * F), Seg3Combine(), s));
+                                    (size_t)(n * F), Seg3Combine(), s));
 }
 
 // Writes out[0] = 0 and out[1..n] = inclusive scan of in[0], in[stride], ...
@@ -1717,11 +1793,13 @@ void register_gpu(py::module_& m) {
   m.def("gpu_scan_records", &gpu_scan_records, py::arg("data"), py::arg("off"),
         py::arg("len"), py::arg("R"), py::arg("fmt"), py::arg("schema_blob"),
         py::arg("F"), py::arg("stats"), py::arg("err"), py::arg("crc_err"),
-        py::arg("stream"), py::arg("avg_bytes") = 0);
+        py::arg("stream"), py::arg("avg_bytes") = 0, py::arg("rec_base") = 0,
+        py::arg("max_blocks") = 0);
   m.def("gpu_extract_fields", &gpu_extract_fields, py::arg("data"),
         py::arg("R"), py::arg("F"), py::arg("stats"), py::arg("metas"),
         py::arg("meta_dev"), py::arg("err"), py::arg("stream"),
-        py::arg("avg_bytes") = 0);
+        py::arg("avg_bytes") = 0, py::arg("r0") = 0,
+        py::arg("max_blocks") = 0);
   m.def("gpu_size_records", &gpu_size_records);
   m.def("gpu_emit_records", &gpu_emit_records, py::arg("cols_dev"),
         py::arg("schema_blob"), py::arg("fmt"), py::arg("r0"), py::arg("R"),
@@ -1733,13 +1811,18 @@ void register_gpu(py::module_& m) {
   m.def("gpu_frame_scan_blocks", &gpu_frame_scan_blocks);
   m.def("gpu_frame_scan_count", &gpu_frame_scan_count);
   m.def("gpu_frame_scan_emit", &gpu_frame_scan_emit);
+  m.def("gpu_frame_chain", &gpu_frame_chain);
   m.def("gpu_gather_payloads", &gpu_gather_payloads, py::arg("data"),
         py::arg("off"), py::arg("len"), py::arg("dst_off"), py::arg("R"),
         py::arg("out"), py::arg("stream"), py::arg("avg_bytes") = 0);
   m.def("gpu_infer_codes", &gpu_infer_codes);
   m.def("gpu_scan_temp_bytes", &gpu_scan_temp_bytes);
   m.def("gpu_stat_scan_temp_bytes", &gpu_stat_scan_temp_bytes);
-  m.def("gpu_stat_scans", &gpu_stat_scans);
+  m.def("gpu_stat_scans", &gpu_stat_scans, py::arg("temp"),
+        py::arg("temp_bytes"), py::arg("stats"), py::arg("R"), py::arg("F"),
+        py::arg("val_base"), py::arg("byte_base"), py::arg("list_base"),
+        py::arg("stream"), py::arg("r0") = 0, py::arg("r1") = -1,
+        py::arg("stride") = 0);
   m.def("gpu_excl_sum_strided", &gpu_excl_sum_strided);
   m.def("file_mmap_pinned", &file_mmap_pinned, py::arg("path"), py::arg("n"),
         py::arg("writable"));

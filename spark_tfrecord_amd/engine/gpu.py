@@ -1,8 +1,9 @@
 """GPU engine: gfx950 kernel pipeline orchestration.
 
-Decode: sliced H2D (file-mapping DMA) overlapped with the two-pass frame
-scan -> chain validation -> fused structure-scan+CRC -> rocprim strided
-prefix sums -> extract_fields -> device wire-form columns.
+Decode: sliced H2D (file-mapping DMA); per arrived slice, under the later
+slices' DMA: two-pass frame scan -> chain check -> fused structure-scan+CRC
+-> ranged rocprim prefix sums -> extract_fields -> device wire-form
+columns. decode_device is the same pipeline over a whole resident image.
 Encode: device wire-form -> size_records -> prefix sum -> record-range
 sliced fused emit+CRC overlapped with the D2H DMA into the file mapping.
 
@@ -20,6 +21,7 @@ import numpy as np
 import torch
 
 from .. import _native
+from . import stream_plan
 from ..columnar import RecordBatch, WireColumn, schema_blob, wire_fields
 from ..schema import KIND_BYTES, KIND_FLOAT, KIND_INT64, StructType, is_sequence_field, wire_kind_of
 
@@ -83,14 +85,31 @@ def pinned_buffer(tag: str, nbytes: int) -> torch.Tensor:
 
 _CHUNK = 64 << 20  # 64 MiB: overlap file IO with PCIe copies chunkwise
 # engine knobs: overridable via env for tuning
-_READ_SLICE = int(os.environ.get("TFREC_READ_SLICE", 48 << 20))
+# 32 MiB: the work of the last slice(s) is the decode tail, so smaller
+# slices shorten it until the per-slice host round trips stop fitting under
+# the copies (measured 64/48/32/24/16 MiB: 9.14/8.99/8.84/8.86/9.44 ms per
+# flagship step).
+_READ_SLICE = int(os.environ.get("TFREC_READ_SLICE", 32 << 20))
+# Each slice is copied half on either DMA stream. The streams share the
+# link, so whole slices alternating between them land in pairs and the tail
+# holds a pair's work (9.18 ms); TFREC_READ_SPLIT=0 restores that.
+_SPLIT_SLICES = os.environ.get("TFREC_READ_SPLIT", "1") != "0"
 _WRITE_SLICES = int(os.environ.get("TFREC_WRITE_SLICES", 8))
-# Prescan (structure-scan the arrived prefix under the tail DMA) measured
-# NET-NEGATIVE on this host: every host<->device copy executes as a blit
-# KERNEL (no SDMA for host-registered or torch-pinned memory — see
-# exp/exp_sdma.py), so "overlapped" compute contends with the copy kernels
-# and the extra syncs cost more than the hidden scan. Off by default.
-_PRESCAN = os.environ.get("TFREC_PRESCAN", "0") == "1"
+# Streamed decode: the pipelined reader discovers, chain-checks and
+# structure-scans each slice's records while later slices are still in DMA
+# flight. TFREC_STREAM_DECODE=0 forces the unstreamed path (COUNT under the
+# DMA, everything else after the last slice).
+_STREAM_DECODE = os.environ.get("TFREC_STREAM_DECODE", "1") != "0"
+# Row buffers of the streamed path are sized from the record density of the
+# first slice that yields records, times this headroom; a launch that would
+# not fit regrows them by copy.
+_STREAM_HEADROOM = float(os.environ.get("TFREC_STREAM_HEADROOM", 1.125))
+# Grid cap of the scan launches that run under in-flight copies (0 = the
+# launch wrapper's own cap).
+_STREAM_MAX_BLOCKS = int(os.environ.get("TFREC_STREAM_MAX_BLOCKS", 0))
+# Also run the stat prefix sums and the value extraction per arrived slice
+# (0: once over the whole file after the last slice).
+_STREAM_EXTRACT = os.environ.get("TFREC_STREAM_EXTRACT", "1") != "0"
 # msync mapped-DMA writes before the publishing rename (durability parity
 # with write_file_atomic's fsync; near-free on tmpfs). TFREC_SYNC=0 disables.
 _SYNC_WRITES = os.environ.get("TFREC_SYNC", "1") != "0"
@@ -261,6 +280,16 @@ def _excl_sum_into(out_ptr: int, in_ptr: int, stride: int, n: int, device):
                                  out_ptr, n, _stream())
 
 
+def _stat_scan_workspace(R: int, F: int, device) -> torch.Tensor:
+    key = ("stat", device.index if hasattr(device, "index") else 0)
+    need = _native.gpu_stat_scan_temp_bytes(R, F)
+    ws = _scan_ws.get(key)
+    if ws is None or ws.numel() < need:
+        ws = torch.empty(int(need * 2) or 1, dtype=torch.uint8, device=device)
+        _scan_ws[key] = ws
+    return ws
+
+
 def excl_sum(t: torch.Tensor) -> torch.Tensor:
     """Contiguous 1-D int64 tensor -> (n+1)-long exclusive scan, total at [-1]."""
     n = t.numel()
@@ -314,51 +343,6 @@ def scan_frames_device(data: torch.Tensor):
                                  block_counts.data_ptr(), _stream())
     off, lens, _ = _emit_and_chain(data, [(0, N)], block_counts, N)
     return off, lens
-
-
-def _prescan_prefix(data, pre_ranges, block_counts, nblocks, N, arrived,
-                    schema, record_type):
-    """Emit the candidates of the ALREADY-ARRIVED slice prefix and launch
-    the structure scan for every record that lies entirely within `arrived`
-    bytes — on the main stream, which at this point is NOT yet ordered
-    after the in-flight tail slices, so this work overlaps their DMA.
-    Returns (stats1[K,F,6], err1, K) for decode_device, or None."""
-    device = data.device
-    nb_pre = sum(nblocks[:len(pre_ranges)])
-    if nb_pre == 0:
-        return None
-    block_off = excl_sum(block_counts[:nb_pre])
-    C = int(block_off[-1].item())  # syncs main: prefix counts only
-    if C == 0:
-        return None
-    pos = torch.empty(C, dtype=torch.int64, device=device)
-    lens = torch.empty(C, dtype=torch.int64, device=device)
-    base = 0
-    for s, e in pre_ranges:
-        _native.gpu_frame_scan_emit(data.data_ptr(), N, s, e, base,
-                                    block_off.data_ptr(), pos.data_ptr(),
-                                    lens.data_ptr(), _stream())
-        base += _native.gpu_frame_scan_blocks(s, e)
-    # records fully inside the arrived prefix (candidates are sorted)
-    K = int(torch.searchsorted(pos + 16 + lens, torch.tensor(
-        arrived + 1, device=device)).item())
-    if K == 0:
-        return None
-    fields = wire_fields(schema)
-    F = len(fields)
-    if F == 0:
-        return None
-    blob = torch.frombuffer(bytearray(schema_blob(schema)),
-                            dtype=torch.uint8).to(device)
-    stats1 = torch.empty((K, F, 6), dtype=torch.int64, device=device)
-    err1 = torch.zeros(2, dtype=torch.int32, device=device)
-    off1 = (pos[:K] + 12).contiguous()
-    lens1 = lens[:K].contiguous()
-    _native.gpu_scan_records(data.data_ptr(), off1.data_ptr(),
-                             lens1.data_ptr(), K, FMT[record_type],
-                             blob.data_ptr(), F, stats1.data_ptr(),
-                             err1.data_ptr(), 0, _stream())
-    return stats1, err1, K
 
 
 def _emit_and_chain(data, ranges, block_counts, N):
@@ -430,10 +414,8 @@ def crc_verify_device(data: torch.Tensor, off: torch.Tensor, lens: torch.Tensor,
 
 def decode_device(data: torch.Tensor, off: torch.Tensor, lens: torch.Tensor,
                   schema: StructType, record_type: str,
-                  verify_crc: bool = True, prescan=None) -> RecordBatch:
-    """Decode framed records already resident in HBM into device wire-form.
-    `prescan` = (stats1, err1, K) from _prescan_prefix: rows [0, K) were
-    already structure-scanned while the tail of the file was in DMA flight."""
+                  verify_crc: bool = True) -> RecordBatch:
+    """Decode framed records already resident in HBM into device wire-form."""
     check_native()
     device = data.device
     R = off.numel()
@@ -464,17 +446,15 @@ def decode_device(data: torch.Tensor, off: torch.Tensor, lens: torch.Tensor,
                 for f in fields]
         return RecordBatch(schema, cols, R)
 
-    blob = torch.frombuffer(bytearray(schema_blob(schema)),
-                            dtype=torch.uint8).to(device)
+    blob = _schema_blob_device(schema, device)
     # FieldStat[R][F] as int64 [R,F,6]: pos,len,nvals,nbytes,nlists,(kind|err)
     stats = torch.empty((R, F, 6), dtype=torch.int64, device=device)
     # err buffers are int32[2]: (codec error code, 1 + offending record index)
     err = torch.zeros(2, dtype=torch.int32, device=device)
     # frame CRC verification is FUSED into the structure scan: the record
     # bytes are CRC'd while L2-hot from the parse. (A concurrent side-stream
-    # CRC pass was tried and reverted: every host<->device copy on this
-    # stack is a blit KERNEL, so "free" overlap doesn't exist and the fused
-    # form has ~1 ms less total GPU work per 215 MB.)
+    # CRC pass was tried and reverted: it is a second full read of the
+    # file, and the fused form has ~1 ms less total GPU work per 215 MB.)
     # NOTE: for Example/SequenceExample the CRC stays FUSED into the scan at
     # any record size — the serial protobuf parse dominates huge records, so
     # a separate wave-CRC pass only adds a second full read (measured).
@@ -483,35 +463,13 @@ def decode_device(data: torch.Tensor, off: torch.Tensor, lens: torch.Tensor,
     fuse_crc = verify_crc
     if fuse_crc:
         crc_err = torch.full((1,), -1, dtype=torch.int64, device=device)
-    r0 = 0
-    err1 = None
-    if prescan is not None:
-        stats1, err1, K = prescan
-        if K <= R and stats1.shape[1] == F:
-            stats[:K].copy_(stats1)
-            r0 = K
-        else:
-            err1 = None
     # average record size steers the one-per-lane vs one-per-wave kernels
     avg_bytes = max(0, (data.numel() // R) - 16) if R else 0
-    if R > r0:
-        stride = F * 6 * 8
-        _native.gpu_scan_records(data.data_ptr(), off.data_ptr() + r0 * 8,
-                                 lens.data_ptr() + r0 * 8, R - r0,
-                                 FMT[record_type], blob.data_ptr(), F,
-                                 stats.data_ptr() + r0 * stride,
-                                 err.data_ptr(),
-                                 crc_err.data_ptr() if fuse_crc else 0,
-                                 _stream(), avg_bytes)
-    crc_err_pre = None
-    if fuse_crc and r0 > 0:
-        # prescanned rows skipped the fused path: verify them separately.
-        # Separate error buffer — the fused kernel reports indices relative
-        # to its r0-based sub-launch, this one reports absolute indices.
-        crc_err_pre = torch.full((1,), -1, dtype=torch.int64, device=device)
-        _native.gpu_crc_verify(data.data_ptr(), off.data_ptr(),
-                               lens.data_ptr(), r0, crc_err_pre.data_ptr(),
-                               _stream(), 0)
+    _native.gpu_scan_records(data.data_ptr(), off.data_ptr(), lens.data_ptr(),
+                             R, FMT[record_type], blob.data_ptr(), F,
+                             stats.data_ptr(), err.data_ptr(),
+                             crc_err.data_ptr() if fuse_crc else 0,
+                             _stream(), avg_bytes)
 
     # Per-field exclusive prefix sums ([F, R+1] x 3 planes) in ONE rocprim
     # launch: a head-flag segmented scan over the [F*R] triple sequence
@@ -522,46 +480,74 @@ def decode_device(data: torch.Tensor, off: torch.Tensor, lens: torch.Tensor,
     val_base[:, 0] = 0
     byte_base[:, 0] = 0
     list_base[:, 0] = 0
-    key = ("stat", device.index if hasattr(device, "index") else 0)
-    need = _native.gpu_stat_scan_temp_bytes(R, F)
-    ws = _scan_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(int(need * 2) or 1, dtype=torch.uint8, device=device)
-        _scan_ws[key] = ws
+    ws = _stat_scan_workspace(R, F, device)
     _native.gpu_stat_scans(ws.data_ptr(), ws.numel(), stats.data_ptr(), R, F,
                            val_base.data_ptr(), byte_base.data_ptr(),
                            list_base.data_ptr(), _stream())
     totals = torch.stack([val_base[:, -1], byte_base[:, -1], list_base[:, -1]])
     totals_h = totals.cpu()  # one sync for all allocations
-    if fuse_crc:
-        bad = int(crc_err.item())
-        # fused-scan indices are relative to the r0-based sub-launch
-        bad_abs = (bad - 1 + r0) if bad != -1 else -1
-        if crc_err_pre is not None:
-            bp = int(crc_err_pre.item())
-            if bp != -1:
-                bad_abs = bp - 1 if bad_abs == -1 else min(bad_abs, bp - 1)
-        if bad_abs != -1:
-            raise RuntimeError(
-                f"corrupt TFRecord: bad CRC in record {bad_abs}")
-    rc = int(err[0].item())
-    rec = int(err[1].item()) - 1 + r0  # scan indices are relative to r0
-    if rc == 0 and err1 is not None:
-        rc = int(err1[0].item())
-        rec = int(err1[1].item()) - 1  # prescan launch base is record 0
+    _raise_scan_errors(int(crc_err.item()) if fuse_crc else -1,
+                       int(err[0].item()), int(err[1].item()))
+    cols = _extract_columns(data, R, fields, stats, val_base, byte_base,
+                            list_base, totals_h, err, avg_bytes)
+    if int(err[0].item()) != 0:
+        _raise_extract_error(int(err[0].item()), int(err[1].item()))
+    return RecordBatch(schema, cols, R)
+
+
+_schema_blobs = {}
+
+
+def _schema_blob_device(schema: StructType, device) -> torch.Tensor:
+    """Device copy of the schema blob, cached per (blob bytes, device): a
+    schema does not change between reads, and the upload is a pageable,
+    synchronous copy."""
+    raw = bytes(schema_blob(schema))
+    key = (raw, str(torch.device(device)))
+    blob = _schema_blobs.get(key)
+    if blob is None:
+        if len(_schema_blobs) >= 64:
+            _schema_blobs.clear()
+        blob = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(device)
+        _schema_blobs[key] = blob
+    return blob
+
+
+def _raise_scan_errors(crc_bad: int, rc: int, rec1: int):
+    """Structure-scan outcome -> exception. crc_bad is the fused CRC word (-1
+    clean, else 1 + first bad record), (rc, rec1) the codec error pair (rec1
+    = 1 + offending record). A bad CRC takes precedence."""
+    if crc_bad != -1:
+        raise RuntimeError(f"corrupt TFRecord: bad CRC in record {crc_bad - 1}")
     if rc != 0:
+        rec = rec1 - 1
         where = f" in record {rec}" if rec >= 0 else ""
         raise RuntimeError(f"TFRecord decode failed{where} (native error "
                            f"{rc}; kind mismatch or malformed record)")
 
+
+def _raise_extract_error(rc: int, rec1: int):
+    rec = rec1 - 1
+    where = f" (record {rec})" if rec >= 0 else ""
+    raise RuntimeError(f"TFRecord decode failed in value extraction"
+                       f"{where} (native error {rc})")
+
+
+def _extract_columns(data, R, fields, stats, val_base, byte_base, list_base,
+                     totals_h, err, avg_bytes) -> List[WireColumn]:
+    """Allocate the value buffers from the host totals ([3][F]: values,
+    bytes, lists per field), launch the extraction over records [0, R) and
+    assemble the columns. stats is [R,F,6]; the base planes are [F][R+1]."""
+    device = data.device
+    F = len(fields)
     metas = []
     outs = []
     for i, f in enumerate(fields):
         kind = wire_kind_of(f.dataType)
         seq = is_sequence_field(f.dataType)
-        nv = int(totals_h[0, i])
-        nb = int(totals_h[1, i])
-        nl = int(totals_h[2, i])
+        nv = int(totals_h[0][i])
+        nb = int(totals_h[1][i])
+        nl = int(totals_h[2][i])
         o = {"kind": kind, "seq": seq}
         o["i64_vals"] = torch.empty(nv if kind == KIND_INT64 else 0,
                                     dtype=torch.int64, device=device)
@@ -605,12 +591,7 @@ def decode_device(data: torch.Tensor, off: torch.Tensor, lens: torch.Tensor,
                   o["f32_vals"] if kind == KIND_FLOAT else o["bytes_data"])
         cols.append(WireColumn(kind, seq, presence, val_base[i], values,
                                elem_off, list_base[i] if seq else None, sub_off))
-    if int(err[0].item()) != 0:
-        rec = int(err[1].item()) - 1
-        where = f" (record {rec})" if rec >= 0 else ""
-        raise RuntimeError(f"TFRecord decode failed in value extraction"
-                           f"{where} (native error {int(err[0].item())})")
-    return RecordBatch(schema, cols, R)
+    return cols
 
 
 def decode_buffer_device(data_np: np.ndarray, schema: StructType, record_type: str,
@@ -757,13 +738,24 @@ def write_batch_to_file(batch: RecordBatch, path: str,
     return total
 
 
+# what the last read_file_to_batch_pipelined call on a registered mapping did:
+# path = "streamed" | "fallback" (streamed attempt abandoned) | "unstreamed"
+# (TFREC_STREAM_DECODE=0), the slice count and the row-buffer regrows
+last_read = {}
+
+
 def read_file_to_batch_pipelined(path: str, schema: StructType, record_type: str,
                                  verify_crc: bool = True,
                                  device="cuda") -> RecordBatch:
-    """File -> device batch with the H2D DMA sliced so the frame-candidate
-    scan of slice k runs while slice k+1 is still in flight. Positions within
-    32 bytes of a slice boundary are deferred to the next slice's launch
-    (their load window extends past the boundary)."""
+    """File -> device batch with the H2D DMA sliced so the work on slice k
+    runs while slice k+1 is still in flight: frame discovery (COUNT, prefix
+    sum, EMIT), the chain check and the fused structure scan + CRC of the
+    records that have fully arrived. Positions within 32 bytes of a slice
+    boundary are deferred to the next slice's launch (their load window
+    extends past the boundary). After the last slice only that slice's work,
+    the stat prefix sums and the extraction remain. A broken frame chain
+    abandons the streamed attempt for the whole-file _emit_and_chain +
+    decode_device, which is also what TFREC_STREAM_DECODE=0 runs."""
     import os as _os
 
     check_native()
@@ -779,78 +771,362 @@ def read_file_to_batch_pipelined(path: str, schema: StructType, record_type: str
         off, lens = scan_frames_device(data)
         return decode_device(data, off, lens, schema, record_type, verify_crc)
     data = torch.empty(n, dtype=torch.uint8, device=device)
-    span = _READ_SLICE
-    S = max(1, (n + span - 1) // span)
-    # pre-size the per-block count buffer over the slice ranges
-    ranges = []
-    scanned = 0
-    for s in range(S):
-        b1 = min(n, (s + 1) * span)
-        scan_end = b1 - 32 if s < S - 1 else n
-        if scan_end > scanned:
-            ranges.append((scanned, scan_end))
-            scanned = scan_end
-    nblocks = [int(_native.gpu_frame_scan_blocks(a, b)) for a, b in ranges]
+    device = data.device
+    plan = stream_plan.plan_slices(n, _READ_SLICE)
+    S = len(plan)
+    # pre-size the per-block count buffer over the slice scan ranges
+    nblocks = [int(_native.gpu_frame_scan_blocks(p.scan_lo, p.scan_hi))
+               if p.scan_hi > p.scan_lo else 0 for p in plan]
     block_counts = torch.empty(max(sum(nblocks), 1), dtype=torch.int64,
                                device=device)
     main = torch.cuda.current_stream()
     streams = _dma_streams()
     # issue ALL H2D slices up front on the side streams; per-slice events
-    # let the main stream gate each count pass on just its own slice
+    # let the main stream gate each slice's work on just its own slice
     events = []
     for st in streams:
         st.wait_stream(main)  # `data` allocation ordering
-    for s in range(S):
-        b0, b1 = s * span, min(n, (s + 1) * span)
-        st = streams[s % len(streams)]
-        _native.gpu_memcpy_h2d(data.data_ptr() + b0, ptr + b0, b1 - b0,
-                               st.cuda_stream)
-        ev = torch.cuda.Event()
-        ev.record(st)
-        events.append(ev)
+    for s, p in enumerate(plan):
+        # each slice goes half on either DMA stream: the streams share the
+        # link, so whole slices alternating between them land in PAIRS;
+        # split, slice k lands alone while k+1 is still in flight
+        half = (p.b1 - p.b0) // 2 if _SPLIT_SLICES and len(streams) > 1 else 0
+        parts = ([(p.b0, p.b0 + half, 0), (p.b0 + half, p.b1, 1)] if half
+                 else [(p.b0, p.b1, s % len(streams))])
+        evs = []
+        for lo, hi, k in parts:
+            st = streams[k]
+            _native.gpu_memcpy_h2d(data.data_ptr() + lo, ptr + lo, hi - lo,
+                                   st.cuda_stream)
+            ev = torch.cuda.Event()
+            ev.record(st)
+            evs.append(ev)
+        events.append(evs)
     data.record_stream(streams[0])
     if len(streams) > 1:
         data.record_stream(streams[1])
 
-    def launch_counts(ri: int, base: int):
-        _native.gpu_frame_scan_count(data.data_ptr(), n, ranges[ri][0],
-                                     ranges[ri][1], base,
-                                     block_counts.data_ptr(), _stream())
+    fields = wire_fields(schema)
+    F = len(fields)
+    streaming = _STREAM_DECODE
+    last_read.update(path="streamed", slices=S, regrows=0)
+    do_scan = streaming and record_type != "ByteArray" and F > 0
+    fuse_crc = verify_crc
+    vals = None
+    if streaming:
+        # one int64 status block, read back whole: [0] broken-chain flag,
+        # [1] fused CRC word (all-ones = clean), [2] the scan's int32 codec
+        # error pair, [3] the extraction's, [4 + j] end of the j-th chain
+        # launch's last candidate (word 4 is the carry into the first: 0)
+        status = torch.zeros(_ST_CARRY + 1 + S, dtype=torch.int64,
+                             device=device)
+        status[_ST_CRC] = -1
+        sp = status.data_ptr()
+        err = status[_ST_ERR:_ST_ERR + 1].view(torch.int32)
+        xerr = status[_ST_XERR:_ST_XERR + 1].view(torch.int32)
+        rows = _StreamRows(n, F if do_scan else 0, device)
+        if do_scan:
+            blob = _schema_blob_device(schema, device)
+            vals = _StreamValues(fields, n, device) if _STREAM_EXTRACT else None
+            meta_dev = torch.empty(F * _native.gpu_devmeta_bytes(),
+                                   dtype=torch.uint8, device=device)
 
-    # stage point: once ~2/3 of the slices have landed, scan the records that
-    # are fully inside the arrived prefix WHILE the tail slices are still in
-    # DMA flight (hides most of the structure-scan under the H2D)
-    k0 = ((2 * S) // 3 if _PRESCAN and S >= 3 and record_type != "ByteArray"
-          else 0)
-
-    ri = 0
-    base = 0
-
-    def consume_slices(upto: int):
-        nonlocal ri, base
-        for s in range(upto):
-            if events[s] is None:
+    base = 0    # block_counts offset of the current slice
+    C = 0       # chained candidates so far
+    nchain = 0  # chain launches so far
+    r_done = 0  # records structure-scanned so far
+    pending = None  # the last slice's rows: extracted after the readback
+    avg_bytes = None
+    for s, p in enumerate(plan):
+        for ev in events[s]:
+            main.wait_event(ev)
+        last = s == S - 1
+        nb = nblocks[s]
+        if nb:
+            _native.gpu_frame_scan_count(data.data_ptr(), n, p.scan_lo,
+                                         p.scan_hi, base,
+                                         block_counts.data_ptr(), _stream())
+        if not streaming:
+            base += nb
+            continue
+        if nb:
+            # host syncs below cost nothing while later slices are in flight
+            block_off = excl_sum(block_counts[base:base + nb])
+            c_s = int(block_off[-1].item())
+            base += nb
+            if c_s:
+                rows.reserve(C + c_s, C, r_done, p.scan_hi)
+                _native.gpu_frame_scan_emit(
+                    data.data_ptr(), n, p.scan_lo, p.scan_hi, 0,
+                    block_off.data_ptr(), rows.pos.data_ptr() + C * 8,
+                    rows.lens.data_ptr() + C * 8, _stream())
+                _native.gpu_frame_chain(
+                    rows.pos.data_ptr() + C * 8, rows.lens.data_ptr() + C * 8,
+                    c_s, sp + (_ST_CARRY + nchain) * 8,
+                    sp + (_ST_CARRY + 1 + nchain) * 8,
+                    rows.off.data_ptr() + C * 8, sp + _ST_BROKEN * 8, _stream())
+                nchain += 1
+                C += c_s
+        if not do_scan or C == r_done:
+            continue
+        if last:
+            # every candidate ends inside the file (the COUNT cull), so all
+            # of them have arrived; the chain flag rides the final readback
+            avail = C
+            end = n
+        else:
+            st_h = status.cpu()
+            if int(st_h[_ST_BROKEN]) != 0:
+                streaming = do_scan = False  # finish the COUNT passes only
                 continue
-            main.wait_event(events[s])
-            events[s] = None
-            scan_end = min(n, (s + 1) * span) - 32 if s < S - 1 else n
-            if ri < len(ranges) and ranges[ri][1] == scan_end:
-                launch_counts(ri, base)
-                base += nblocks[ri]
-                ri += 1
+            end = int(st_h[_ST_CARRY + nchain])
+            avail = stream_plan.arrived_records(C, end, p.b1)
+            if avail < C:
+                end = p.b1
+        if avail > r_done:
+            if avg_bytes is None:  # wave/lane choice: once per file
+                avg_bytes = max(0, end // avail - 16)
+            _native.gpu_scan_records(
+                data.data_ptr(), rows.off.data_ptr() + r_done * 8,
+                rows.lens.data_ptr() + r_done * 8, avail - r_done,
+                FMT[record_type], blob.data_ptr(), F,
+                rows.stats.data_ptr() + r_done * F * 48, err.data_ptr(),
+                sp + _ST_CRC * 8 if fuse_crc else 0, _stream(), avg_bytes,
+                rec_base=r_done, max_blocks=0 if last else _STREAM_MAX_BLOCKS)
+            if vals is not None:
+                rows.scan_stats(r_done, avail)
+                if last:
+                    pending = (r_done, avail)
+                elif vals.ok:
+                    # running totals + error words of the rows scanned so
+                    # far: extraction only ever sees rows that scanned clean
+                    h = torch.cat(rows.totals(avail)
+                                  + [status[:_ST_CARRY]]).cpu()
+                    pair = h[3 * F + _ST_ERR:3 * F + _ST_ERR + 1].view(torch.int32)
+                    if int(h[3 * F + _ST_CRC]) != -1 or int(pair[0]) != 0:
+                        vals.ok = False  # keep scanning; raised at the end
+                    else:
+                        vals.extract(data, rows, r_done, avail,
+                                     h[:3 * F].view(3, F), end, meta_dev,
+                                     xerr, avg_bytes,
+                                     _STREAM_MAX_BLOCKS)
+            r_done = avail
 
-    prescan = None
-    if k0:
-        consume_slices(k0)  # main now ordered after the first k0 slices ONLY
-        prescan = _prescan_prefix(data, ranges[:ri], block_counts, nblocks, n,
-                                  arrived=min(n, k0 * span), schema=schema,
-                                  record_type=record_type)
-    consume_slices(S)
-    off, lens, clean = _emit_and_chain(data, ranges, block_counts, n)
-    if not clean:
-        prescan = None  # host-stitched chain: prescanned rows are stale
-    return decode_device(data, off, lens, schema, record_type, verify_crc,
-                         prescan=prescan)
+    def unstreamed():
+        last_read["path"] = "fallback" if _STREAM_DECODE else "unstreamed"
+        ranges = [(p.scan_lo, p.scan_hi) for p in plan if p.scan_hi > p.scan_lo]
+        off, lens, _ = _emit_and_chain(data, ranges, block_counts, n)
+        return decode_device(data, off, lens, schema, record_type, verify_crc)
+
+    if not streaming or C == 0:
+        return unstreamed()
+    R = C
+    if not do_scan:
+        st_h = status.cpu()
+        if int(st_h[_ST_BROKEN]) != 0 or int(st_h[_ST_CARRY + nchain]) != n:
+            return unstreamed()
+        return decode_device(data, rows.off[:R], rows.lens[:R], schema,
+                             record_type, verify_crc)
+
+    stats = rows.stats[:R]
+    if vals is None:
+        rows.scan_stats(0, R)
+    # ONE packed readback: totals, then the status block
+    packed = torch.cat(rows.totals(R) + [status]).cpu()
+    st_h = packed[3 * F:]
+    if int(st_h[_ST_BROKEN]) != 0 or int(st_h[_ST_CARRY + nchain]) != n:
+        return unstreamed()
+    pair = st_h[_ST_ERR:_ST_ERR + 1].view(torch.int32)
+    _raise_scan_errors(int(st_h[_ST_CRC]) if fuse_crc else -1, int(pair[0]),
+                       int(pair[1]))
+    totals_h = packed[:3 * F].view(3, F)
+    val_base, byte_base, list_base = rows.planes
+    if vals is None:
+        cols = _extract_columns(data, R, fields, stats,
+                                val_base[:, :R + 1], byte_base[:, :R + 1],
+                                list_base[:, :R + 1], totals_h, xerr,
+                                max(0, n // R - 16))
+    else:
+        # everything before the last slice's rows was extracted under the DMA
+        if not vals.ok:
+            raise RuntimeError("streamed decode: scan error lost")
+        if pending is not None:
+            vals.extract(data, rows, pending[0], pending[1], totals_h, n,
+                         meta_dev, xerr, avg_bytes, 0)
+        cols = vals.columns(stats, val_base, list_base, R)
+    err_h = xerr.cpu()
+    if int(err_h[0]) != 0:
+        _raise_extract_error(int(err_h[0]), int(err_h[1]))
+    return RecordBatch(schema, cols, R)
+
+
+# words of the streamed read's status block
+_ST_BROKEN, _ST_CRC, _ST_ERR, _ST_XERR, _ST_CARRY = 0, 1, 2, 3, 4
+
+
+class _StreamRows:
+    """Row-indexed buffers of one streamed read: candidate pos/len, payload
+    off and (F > 0) the FieldStat rows. Sized from the record density of the
+    first slice that yields candidates times _STREAM_HEADROOM; reserve() is
+    called on the host before every launch that writes rows, and regrows by
+    copying the filled rows when the launch would not fit."""
+
+    def __init__(self, total_bytes: int, F: int, device):
+        self.total_bytes = total_bytes
+        self.F = F
+        self.device = device
+        self.cap = 0
+        self.pos = self.lens = self.off = self.stats = None
+        # exclusive prefix sums of nvals/nbytes/nlists, [F][cap + 1] each;
+        # row f cut to [:R + 1] is the contiguous row_off of field f
+        self.planes = None
+
+    def _alloc(self, cap: int):
+        i64 = dict(dtype=torch.int64, device=self.device)
+        planes = None
+        if self.F:
+            planes = [torch.empty((self.F, cap + 1), **i64) for _ in range(3)]
+            for t in planes:
+                t[:, 0] = 0
+        return (torch.empty(cap, **i64), torch.empty(cap, **i64),
+                torch.empty(cap, **i64),
+                torch.empty((cap, self.F, 6), **i64) if self.F else None,
+                planes)
+
+    def scan_stats(self, r0: int, r1: int):
+        """Ranged stat prefix sums over scanned rows [r0, r1): carries on
+        from the running totals at plane[f][r0]."""
+        ws = _stat_scan_workspace(r1 - r0, self.F, self.device)
+        v, b, l = self.planes
+        _native.gpu_stat_scans(ws.data_ptr(), ws.numel(),
+                               self.stats.data_ptr(), r1, self.F, v.data_ptr(),
+                               b.data_ptr(), l.data_ptr(), _stream(), r0=r0,
+                               r1=r1, stride=self.cap + 1)
+
+    def totals(self, r: int) -> list:
+        """Running totals after r rows: three [F] device views."""
+        return [t[:, r] for t in self.planes]
+
+    def reserve(self, need: int, n_cand: int, n_scanned: int, bytes_seen: int):
+        """Make room for `need` rows; rows [0, n_cand) of pos/len/off and
+        [0, n_scanned) of stats are live."""
+        cap = stream_plan.grown_capacity(self.cap, need, bytes_seen,
+                                         self.total_bytes, _STREAM_HEADROOM)
+        if cap == self.cap:
+            return
+        pos, lens, off, stats, planes = self._alloc(cap)
+        if n_cand:
+            pos[:n_cand].copy_(self.pos[:n_cand])
+            lens[:n_cand].copy_(self.lens[:n_cand])
+            off[:n_cand].copy_(self.off[:n_cand])
+        if n_scanned and stats is not None:
+            stats[:n_scanned].copy_(self.stats[:n_scanned])
+            for new, old in zip(planes, self.planes):
+                new[:, :n_scanned + 1].copy_(old[:, :n_scanned + 1])
+        self.pos, self.lens, self.off, self.stats = pos, lens, off, stats
+        self.planes = planes
+        if self.cap:
+            last_read["regrows"] = last_read.get("regrows", 0) + 1
+        self.cap = cap
+
+
+class _StreamValues:
+    """Output buffers of the streamed extraction, per field: values (int64
+    or float32), payload bytes, elem_len and sub_count. Sized like the row
+    buffers — density of the first extracted range times _STREAM_HEADROOM —
+    and regrown by copying the filled prefix; extract() checks every
+    capacity against the host-read running totals before it launches."""
+
+    _DIMS = (("i64_vals", 0), ("f32_vals", 0), ("elem_len", 0),
+             ("bytes_data", 1), ("sub_count", 2))
+
+    def __init__(self, fields, total_bytes: int, device):
+        self.total_bytes = total_bytes
+        self.device = device
+        self.ok = True  # False once a scanned range reported an error
+        self.kinds = [wire_kind_of(f.dataType) for f in fields]
+        self.seqs = [is_sequence_field(f.dataType) for f in fields]
+        self.filled = [[0] * len(fields) for _ in range(3)]
+        self.bufs = []
+        for kind in self.kinds:
+            dt = {"i64_vals": torch.int64, "f32_vals": torch.float32,
+                  "elem_len": torch.int64, "bytes_data": torch.uint8,
+                  "sub_count": torch.int64}
+            self.bufs.append({k: torch.empty(0, dtype=d, device=device)
+                              for k, d in dt.items()})
+
+    def _used(self, i: int, name: str) -> bool:
+        kind = self.kinds[i]
+        return {"i64_vals": kind == KIND_INT64, "f32_vals": kind == KIND_FLOAT,
+                "elem_len": kind == KIND_BYTES}.get(name, True)
+
+    def _reserve(self, totals, bytes_seen: int):
+        for i, bufs in enumerate(self.bufs):
+            for name, dim in self._DIMS:
+                if not self._used(i, name):
+                    continue
+                need = int(totals[dim][i])
+                old = bufs[name]
+                cap = stream_plan.grown_capacity(
+                    old.numel(), need, bytes_seen, self.total_bytes,
+                    _STREAM_HEADROOM, min_unit=1)
+                if cap == old.numel():
+                    continue
+                new = torch.empty(cap, dtype=old.dtype, device=self.device)
+                k = self.filled[dim][i]
+                if k:
+                    new[:k].copy_(old[:k])
+                if old.numel():
+                    last_read["regrows"] = last_read.get("regrows", 0) + 1
+                bufs[name] = new
+
+    def extract(self, data, rows, r0: int, r1: int, totals, bytes_seen: int,
+                meta_dev, xerr, avg_bytes: int, max_blocks: int):
+        """Extract records [r0, r1). totals ([3][F], host) are the running
+        totals after row r1: every buffer is grown to hold them first."""
+        self._reserve(totals, bytes_seen)
+        v, b, l = rows.planes
+        metas = []
+        for i, bufs in enumerate(self.bufs):
+            metas.append({
+                "kind": self.kinds[i], "is_seq": 1 if self.seqs[i] else 0,
+                "i64_vals": bufs["i64_vals"].data_ptr(),
+                "f32_vals": bufs["f32_vals"].data_ptr(),
+                "bytes_data": bufs["bytes_data"].data_ptr(),
+                "elem_len": bufs["elem_len"].data_ptr(),
+                "sub_count": bufs["sub_count"].data_ptr(),
+                "val_base": v[i].data_ptr(),
+                "byte_base": b[i].data_ptr(),
+                "list_base": l[i].data_ptr() if self.seqs[i] else 0,
+            })
+        _native.gpu_extract_fields(data.data_ptr(), r1 - r0, len(self.bufs),
+                                   rows.stats.data_ptr(), metas,
+                                   meta_dev.data_ptr(), xerr.data_ptr(),
+                                   _stream(), avg_bytes, r0=r0,
+                                   max_blocks=max_blocks)
+        self.filled = [[int(totals[d][i]) for i in range(len(self.bufs))]
+                       for d in range(3)]
+
+    def columns(self, stats, val_base, list_base, R: int) -> List[WireColumn]:
+        cols = []
+        for i, bufs in enumerate(self.bufs):
+            kind, seq = self.kinds[i], self.seqs[i]
+            nv, nb, nl = (self.filled[d][i] for d in range(3))
+            presence = (stats[:, i, 0] >= 0).to(torch.uint8)
+            elem_off = None
+            if kind == KIND_BYTES:
+                elem_off = excl_sum(bufs["elem_len"][:nv])
+            sub_off = None
+            if seq:
+                sub_off = excl_sum(bufs["sub_count"][:nl])
+            values = (bufs["i64_vals"][:nv] if kind == KIND_INT64 else
+                      bufs["f32_vals"][:nv] if kind == KIND_FLOAT else
+                      bufs["bytes_data"][:nb])
+            cols.append(WireColumn(kind, seq, presence, val_base[i][:R + 1],
+                                   values, elem_off,
+                                   list_base[i][:R + 1] if seq else None,
+                                   sub_off))
+        return cols
 
 
 def gz_device_meta(path: str):

@@ -387,6 +387,16 @@ def write_tfrecord(data, path: str, record_type: str = "Example",
                 P.write_file_atomic(payload, fpath)
                 return len(payload)
 
+            # distinct partition values can share a directory (null and ""
+            # both become the Hive default) and with it the part-file path:
+            # write such a path once, from the last combo that maps to it —
+            # what the sequential host path leaves behind — instead of
+            # racing two pool threads on one rename
+            owner = {}
+            for p, _, _ in ranges:
+                owner[tuple(_partition_dir_value(v) for v in combos[p])] = p
+            ranges = [r for r in ranges if owner[tuple(
+                _partition_dir_value(v) for v in combos[r[0]])] == r[0]]
             for nb in P.shared_pool().map(lambda a: _write_part(*a), ranges):
                 if metrics is not None:
                     metrics.add(nbytes=nb, files=1)
