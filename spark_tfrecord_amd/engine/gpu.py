@@ -15,6 +15,8 @@ step 3). See docs/KERNELS.md for per-kernel design notes and measurements.
 from __future__ import annotations
 
 import os
+import threading
+import warnings
 from typing import List, Optional
 
 import numpy as np
@@ -27,8 +29,6 @@ from ..schema import KIND_BYTES, KIND_FLOAT, KIND_INT64, StructType, is_sequence
 
 FMT = {"Example": _native.FMT_EXAMPLE, "SequenceExample": _native.FMT_SEQUENCE}
 
-_U64_MAX = 0xFFFFFFFFFFFFFFFF
-
 
 def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
@@ -40,8 +40,6 @@ def _dev(x, dtype, device="cuda") -> torch.Tensor:
     arr = np.ascontiguousarray(x)
     # arrow buffers are read-only and torch warns on wrapping them; the
     # wrapped tensor is only ever read (the .to() below copies to device)
-    import warnings
-
     with warnings.catch_warnings():
         warnings.simplefilter("ignore", UserWarning)
         return torch.as_tensor(arr, dtype=dtype).to(device)
@@ -59,9 +57,7 @@ def check_native():
 # One reusable pinned buffer per purpose, grown geometrically.
 # ---------------------------------------------------------------------------
 
-import threading as _threading
-
-_pinned_tls = _threading.local()
+_pinned_tls = threading.local()
 
 
 def pinned_buffer(tag: str, nbytes: int) -> torch.Tensor:
@@ -104,11 +100,8 @@ _STREAM_DECODE = os.environ.get("TFREC_STREAM_DECODE", "1") != "0"
 # first slice that yields records, times this headroom; a launch that would
 # not fit regrows them by copy.
 _STREAM_HEADROOM = float(os.environ.get("TFREC_STREAM_HEADROOM", 1.125))
-# Grid cap of the scan launches that run under in-flight copies (0 = the
-# launch wrapper's own cap).
-_STREAM_MAX_BLOCKS = int(os.environ.get("TFREC_STREAM_MAX_BLOCKS", 0))
-# Also run the stat prefix sums and the value extraction per arrived slice
-# (0: once over the whole file after the last slice).
+# Also run the value extraction per arrived slice (0: once over the whole
+# file after the last slice).
 _STREAM_EXTRACT = os.environ.get("TFREC_STREAM_EXTRACT", "1") != "0"
 # msync mapped-DMA writes before the publishing rename (durability parity
 # with write_file_atomic's fsync; near-free on tmpfs). TFREC_SYNC=0 disables.
@@ -119,9 +112,7 @@ def read_file_to_device(path: str, device="cuda") -> torch.Tensor:
     """File -> HBM. Fast path: hipHostRegister'd mmap of the file, one DMA
     straight out of the page cache (zero host memcpy). Fallback: pinned
     staging chunks through the native pread worker pool."""
-    import os as _os
-
-    n = _os.path.getsize(path)
+    n = os.path.getsize(path)
     dev_t = torch.empty(max(n, 1), dtype=torch.uint8, device=device)[:n]
     if n:
         ptr, pinned = _native.file_mmap_pinned(path, n, False)
@@ -168,12 +159,10 @@ def _multi_dma(dst: int, src: int, n: int, fn, after_main: bool):
 
 
 def _read_file_staged(path: str, dev: torch.Tensor) -> torch.Tensor:
-    import os as _os
-
     n = dev.numel()
     buf = pinned_buffer("fread", min(n, 2 * _CHUNK) or 1)
     ev = [torch.cuda.Event(), torch.cuda.Event()]
-    fd = _os.open(path, _os.O_RDONLY)
+    fd = os.open(path, os.O_RDONLY)
     try:
         pos = 0
         which = 0
@@ -187,7 +176,7 @@ def _read_file_staged(path: str, dev: torch.Tensor) -> torch.Tensor:
             pos += m
             which ^= 1 if n > _CHUNK else 0
     finally:
-        _os.close(fd)
+        os.close(fd)
     return dev
 
 
@@ -197,8 +186,6 @@ def device_to_file(img: torch.Tensor, path: str):
     page-cache pages (tmpfs: that IS the storage; disk FS: the kernel
     writes back). Fallback: pinned staging + parallel pwrite (a plain
     multi-threaded pwrite to one file serializes on the inode mutex)."""
-    import os as _os
-
     n = img.numel()
     if n == 0:
         open(path, "wb").close()
@@ -221,12 +208,10 @@ def _write_file_staged(img: torch.Tensor, path: str):
     """Fallback writer when hipHostRegister is unavailable: D2H chunks into
     pinned staging overlapped with plain write()s (single-threaded write
     beats a pwrite pool on the per-inode mutex)."""
-    import os as _os
-
     n = img.numel()
     buf = pinned_buffer("fwrite", min(n, 2 * _CHUNK) or 1)
     ev = [torch.cuda.Event(), torch.cuda.Event()]
-    fd = _os.open(path, _os.O_RDWR | _os.O_CREAT, 0o644)
+    fd = os.open(path, os.O_RDWR | os.O_CREAT, 0o644)
     try:
         pos = 0
         which = 0
@@ -248,11 +233,11 @@ def _write_file_staged(img: torch.Tensor, path: str):
             _native.pwrite_parallel(fd, buf.data_ptr() + which * _CHUNK, m, pos)
             pos = nxt
             which = nwhich
-        _os.ftruncate(fd, n)
+        os.ftruncate(fd, n)
         if _SYNC_WRITES:
-            _os.fsync(fd)
+            os.fsync(fd)
     finally:
-        _os.close(fd)
+        os.close(fd)
 
 
 # ---------------------------------------------------------------------------
@@ -371,11 +356,8 @@ def _emit_and_chain(data, ranges, block_counts, N):
         # rare: false-positive candidate inside a payload — stitch on host
         pos_h = pos.cpu().numpy()
         len_h = lens.cpu().numpy()
-        import numpy as _np
-
         keep = []
         cur = 0
-        idx = 0
         pmap = {int(p): i for i, p in enumerate(pos_h)}
         while cur < N:
             i = pmap.get(cur)
@@ -384,7 +366,7 @@ def _emit_and_chain(data, ranges, block_counts, N):
                     f"corrupt TFRecord: broken frame chain at offset {cur}")
             keep.append(i)
             cur = int(pos_h[i] + 16 + len_h[i])
-        sel = torch.as_tensor(_np.asarray(keep, _np.int64), device=device)
+        sel = torch.as_tensor(np.asarray(keep, np.int64), device=device)
         pos = pos[sel]
         lens = lens[sel]
     return pos + 12, lens, ok
@@ -488,8 +470,13 @@ def decode_device(data: torch.Tensor, off: torch.Tensor, lens: torch.Tensor,
     totals_h = totals.cpu()  # one sync for all allocations
     _raise_scan_errors(int(crc_err.item()) if fuse_crc else -1,
                        int(err[0].item()), int(err[1].item()))
-    cols = _extract_columns(data, R, fields, stats, val_base, byte_base,
-                            list_base, totals_h, err, avg_bytes)
+    # every total is known: bytes_seen == total_bytes sizes the buffers exactly
+    vals = _FieldValues(fields, data.numel(), device)
+    meta_dev = torch.empty(F * _native.gpu_devmeta_bytes(), dtype=torch.uint8,
+                           device=device)
+    vals.extract(data, stats, (val_base, byte_base, list_base), 0, R, totals_h,
+                 data.numel(), meta_dev, err, avg_bytes)
+    cols = vals.columns(stats, val_base, list_base, R)
     if int(err[0].item()) != 0:
         _raise_extract_error(int(err[0].item()), int(err[1].item()))
     return RecordBatch(schema, cols, R)
@@ -533,65 +520,97 @@ def _raise_extract_error(rc: int, rec1: int):
                        f"{where} (native error {rc})")
 
 
-def _extract_columns(data, R, fields, stats, val_base, byte_base, list_base,
-                     totals_h, err, avg_bytes) -> List[WireColumn]:
-    """Allocate the value buffers from the host totals ([3][F]: values,
-    bytes, lists per field), launch the extraction over records [0, R) and
-    assemble the columns. stats is [R,F,6]; the base planes are [F][R+1]."""
-    device = data.device
-    F = len(fields)
-    metas = []
-    outs = []
-    for i, f in enumerate(fields):
-        kind = wire_kind_of(f.dataType)
-        seq = is_sequence_field(f.dataType)
-        nv = int(totals_h[0][i])
-        nb = int(totals_h[1][i])
-        nl = int(totals_h[2][i])
-        o = {"kind": kind, "seq": seq}
-        o["i64_vals"] = torch.empty(nv if kind == KIND_INT64 else 0,
-                                    dtype=torch.int64, device=device)
-        o["f32_vals"] = torch.empty(nv if kind == KIND_FLOAT else 0,
-                                    dtype=torch.float32, device=device)
-        o["bytes_data"] = torch.empty(nb, dtype=torch.uint8, device=device)
-        o["elem_len"] = torch.empty(nv if kind == KIND_BYTES else 0,
-                                    dtype=torch.int64, device=device)
-        o["sub_count"] = torch.empty(nl, dtype=torch.int64, device=device)
-        outs.append(o)
-        metas.append({
-            "kind": kind, "is_seq": 1 if seq else 0,
-            "i64_vals": o["i64_vals"].data_ptr(),
-            "f32_vals": o["f32_vals"].data_ptr(),
-            "bytes_data": o["bytes_data"].data_ptr(),
-            "elem_len": o["elem_len"].data_ptr(),
-            "sub_count": o["sub_count"].data_ptr(),
-            "val_base": val_base[i].data_ptr(),
-            "byte_base": byte_base[i].data_ptr(),
-            "list_base": list_base[i].data_ptr() if seq else 0,
-        })
+class _FieldValues:
+    """Per-field output buffers of the value extraction: values (int64 or
+    float32), payload bytes, elem_len and sub_count. The one place that
+    builds the metas for gpu_extract_fields and turns filled buffers into
+    WireColumns. extract() grows every buffer to the host-read running
+    totals before it launches: from the value density seen so far times
+    _STREAM_HEADROOM (a regrow copies the filled prefix), which is exactly
+    the totals once bytes_seen == total_bytes, as in decode_device."""
 
-    meta_dev = torch.empty(F * _native.gpu_devmeta_bytes(), dtype=torch.uint8,
-                           device=device)
-    _native.gpu_extract_fields(data.data_ptr(), R, F, stats.data_ptr(), metas,
-                               meta_dev.data_ptr(), err.data_ptr(), _stream(),
-                               avg_bytes)
+    # buffer -> (dtype, the totals row (values, bytes, lists) that sizes it,
+    # the one field kind that fills it; None: every kind)
+    _BUFS = {"i64_vals": (torch.int64, 0, KIND_INT64),
+             "f32_vals": (torch.float32, 0, KIND_FLOAT),
+             "elem_len": (torch.int64, 0, KIND_BYTES),
+             "bytes_data": (torch.uint8, 1, None),
+             "sub_count": (torch.int64, 2, None)}
 
-    cols: List[WireColumn] = []
-    for i, (f, o) in enumerate(zip(fields, outs)):
-        kind = o["kind"]
-        seq = o["seq"]
-        presence = (stats[:, i, 0] >= 0).to(torch.uint8)
-        elem_off = None
-        if kind == KIND_BYTES:
-            elem_off = excl_sum(o["elem_len"])
-        sub_off = None
-        if seq:
-            sub_off = excl_sum(o["sub_count"])
-        values = (o["i64_vals"] if kind == KIND_INT64 else
-                  o["f32_vals"] if kind == KIND_FLOAT else o["bytes_data"])
-        cols.append(WireColumn(kind, seq, presence, val_base[i], values,
-                               elem_off, list_base[i] if seq else None, sub_off))
-    return cols
+    def __init__(self, fields, total_bytes: int, device):
+        self.total_bytes = total_bytes
+        self.device = device
+        self.kinds = [wire_kind_of(f.dataType) for f in fields]
+        self.seqs = [is_sequence_field(f.dataType) for f in fields]
+        self.filled = [[0] * len(fields) for _ in range(3)]
+        self.bufs = [{k: torch.empty(0, dtype=d, device=device)
+                      for k, (d, _, _) in self._BUFS.items()} for _ in fields]
+
+    def _reserve(self, totals, bytes_seen: int):
+        for i, bufs in enumerate(self.bufs):
+            for name, (_, dim, kind) in self._BUFS.items():
+                if kind not in (None, self.kinds[i]):
+                    continue
+                need = int(totals[dim][i])
+                old = bufs[name]
+                cap = stream_plan.grown_capacity(
+                    old.numel(), need, bytes_seen, self.total_bytes,
+                    _STREAM_HEADROOM, min_unit=1)
+                if cap == old.numel():
+                    continue
+                new = torch.empty(cap, dtype=old.dtype, device=self.device)
+                k = self.filled[dim][i]
+                if k:
+                    new[:k].copy_(old[:k])
+                if old.numel():
+                    last_read["regrows"] = last_read.get("regrows", 0) + 1
+                bufs[name] = new
+
+    def extract(self, data, stats, planes, r0: int, r1: int, totals,
+                bytes_seen: int, meta_dev, err, avg_bytes: int):
+        """Extract records [r0, r1). stats is the FieldStat tensor from row
+        0, planes the three [F][stride] prefix-sum planes; totals ([3][F],
+        host) are the running totals after row r1."""
+        self._reserve(totals, bytes_seen)
+        v, b, l = planes
+        metas = []
+        for i, bufs in enumerate(self.bufs):
+            metas.append({
+                "kind": self.kinds[i], "is_seq": 1 if self.seqs[i] else 0,
+                **{name: t.data_ptr() for name, t in bufs.items()},
+                "val_base": v[i].data_ptr(),
+                "byte_base": b[i].data_ptr(),
+                "list_base": l[i].data_ptr() if self.seqs[i] else 0,
+            })
+        _native.gpu_extract_fields(data.data_ptr(), r1 - r0, len(self.bufs),
+                                   stats.data_ptr(), metas,
+                                   meta_dev.data_ptr(), err.data_ptr(),
+                                   _stream(), avg_bytes, r0=r0)
+        self.filled = [[int(totals[d][i]) for i in range(len(self.bufs))]
+                       for d in range(3)]
+
+    def columns(self, stats, val_base, list_base, R: int) -> List[WireColumn]:
+        """Wire columns of rows [0, R), all extracted. stats is [R,F,6];
+        row f of a plane cut to [:R + 1] is field f's row_off / list_off."""
+        cols = []
+        for i, bufs in enumerate(self.bufs):
+            kind, seq = self.kinds[i], self.seqs[i]
+            nv, nb, nl = (self.filled[d][i] for d in range(3))
+            presence = (stats[:, i, 0] >= 0).to(torch.uint8)
+            elem_off = None
+            if kind == KIND_BYTES:
+                elem_off = excl_sum(bufs["elem_len"][:nv])
+            sub_off = None
+            if seq:
+                sub_off = excl_sum(bufs["sub_count"][:nl])
+            values = (bufs["i64_vals"][:nv] if kind == KIND_INT64 else
+                      bufs["f32_vals"][:nv] if kind == KIND_FLOAT else
+                      bufs["bytes_data"][:nb])
+            cols.append(WireColumn(kind, seq, presence, val_base[i][:R + 1],
+                                   values, elem_off,
+                                   list_base[i][:R + 1] if seq else None,
+                                   sub_off))
+        return cols
 
 
 def decode_buffer_device(data_np: np.ndarray, schema: StructType, record_type: str,
@@ -642,6 +661,21 @@ def _check_emit_err(err: torch.Tensor):
         raise RuntimeError(f"TFRecord encode failed: size/emit mismatch{where}")
 
 
+def _size_records(batch: RecordBatch, record_type: str, device):
+    """Upload the column table and size every record's frame. Returns
+    (cols_dev, blob, psize, frame_off): the device column table, the schema
+    blob, the per-record frame sizes and their (R+1)-long exclusive scan."""
+    blob = _schema_blob_device(batch.schema, device)
+    col_dicts = [_col_ptrs(c) for c in batch.columns]
+    cols_dev = torch.empty(_native.gpu_devcols_bytes(len(col_dicts)),
+                           dtype=torch.uint8, device=device)
+    psize = torch.empty(batch.num_rows, dtype=torch.int64, device=device)
+    _native.gpu_size_records(col_dicts, cols_dev.data_ptr(), blob.data_ptr(),
+                             FMT[record_type], batch.num_rows,
+                             psize.data_ptr(), _stream())
+    return cols_dev, blob, psize, excl_sum(psize)
+
+
 def encode_device(batch: RecordBatch, record_type: str) -> torch.Tensor:
     """Device wire-form batch -> framed file image as a device u8 tensor."""
     check_native()
@@ -659,15 +693,7 @@ def encode_device(batch: RecordBatch, record_type: str) -> torch.Tensor:
                                     _stream(), (total // R) - 16)
         return file
 
-    blob = torch.frombuffer(bytearray(schema_blob(batch.schema)),
-                            dtype=torch.uint8).to(device)
-    col_dicts = [_col_ptrs(c) for c in batch.columns]
-    cols_dev = torch.empty(_native.gpu_devcols_bytes(len(col_dicts)),
-                           dtype=torch.uint8, device=device)
-    psize = torch.empty(R, dtype=torch.int64, device=device)
-    _native.gpu_size_records(col_dicts, cols_dev.data_ptr(), blob.data_ptr(),
-                             FMT[record_type], R, psize.data_ptr(), _stream())
-    frame_off = excl_sum(psize)
+    cols_dev, blob, _, frame_off = _size_records(batch, record_type, device)
     total = int(frame_off[-1].item())
     file = torch.empty(total, dtype=torch.uint8, device=device)
     err = torch.zeros(2, dtype=torch.int32, device=device)
@@ -693,15 +719,7 @@ def write_batch_to_file(batch: RecordBatch, path: str,
         device_to_file(img, path)
         return img.numel()
     device = batch.columns[0].presence.device
-    blob = torch.frombuffer(bytearray(schema_blob(batch.schema)),
-                            dtype=torch.uint8).to(device)
-    col_dicts = [_col_ptrs(c) for c in batch.columns]
-    cols_dev = torch.empty(_native.gpu_devcols_bytes(len(col_dicts)),
-                           dtype=torch.uint8, device=device)
-    psize = torch.empty(R, dtype=torch.int64, device=device)
-    _native.gpu_size_records(col_dicts, cols_dev.data_ptr(), blob.data_ptr(),
-                             FMT[record_type], R, psize.data_ptr(), _stream())
-    frame_off = excl_sum(psize)
+    cols_dev, blob, _, frame_off = _size_records(batch, record_type, device)
     S = max(1, min(slices if slices is not None else _WRITE_SLICES, R))
     ridx = [R * s // S for s in range(S + 1)]
     bounds = frame_off[ridx].cpu()  # one sync: slice byte bounds + total
@@ -743,225 +761,46 @@ def write_batch_to_file(batch: RecordBatch, path: str,
 # (TFREC_STREAM_DECODE=0), the slice count and the row-buffer regrows
 last_read = {}
 
-
-def read_file_to_batch_pipelined(path: str, schema: StructType, record_type: str,
-                                 verify_crc: bool = True,
-                                 device="cuda") -> RecordBatch:
-    """File -> device batch with the H2D DMA sliced so the work on slice k
-    runs while slice k+1 is still in flight: frame discovery (COUNT, prefix
-    sum, EMIT), the chain check and the fused structure scan + CRC of the
-    records that have fully arrived. Positions within 32 bytes of a slice
-    boundary are deferred to the next slice's launch (their load window
-    extends past the boundary). After the last slice only that slice's work,
-    the stat prefix sums and the extraction remain. A broken frame chain
-    abandons the streamed attempt for the whole-file _emit_and_chain +
-    decode_device, which is also what TFREC_STREAM_DECODE=0 runs."""
-    import os as _os
-
-    check_native()
-    n = _os.path.getsize(path)
-    if n == 0:
-        z = torch.zeros(0, dtype=torch.int64, device=device)
-        return decode_device(torch.zeros(0, dtype=torch.uint8, device=device),
-                             z, z.clone(), schema, record_type, verify_crc)
-    ptr, pinned = _native.file_mmap_pinned(path, n, False)
-    if not pinned:
-        data = _read_file_staged(path, torch.empty(n, dtype=torch.uint8,
-                                                   device=device))
-        off, lens = scan_frames_device(data)
-        return decode_device(data, off, lens, schema, record_type, verify_crc)
-    data = torch.empty(n, dtype=torch.uint8, device=device)
-    device = data.device
-    plan = stream_plan.plan_slices(n, _READ_SLICE)
-    S = len(plan)
-    # pre-size the per-block count buffer over the slice scan ranges
-    nblocks = [int(_native.gpu_frame_scan_blocks(p.scan_lo, p.scan_hi))
-               if p.scan_hi > p.scan_lo else 0 for p in plan]
-    block_counts = torch.empty(max(sum(nblocks), 1), dtype=torch.int64,
-                               device=device)
-    main = torch.cuda.current_stream()
-    streams = _dma_streams()
-    # issue ALL H2D slices up front on the side streams; per-slice events
-    # let the main stream gate each slice's work on just its own slice
-    events = []
-    for st in streams:
-        st.wait_stream(main)  # `data` allocation ordering
-    for s, p in enumerate(plan):
-        # each slice goes half on either DMA stream: the streams share the
-        # link, so whole slices alternating between them land in PAIRS;
-        # split, slice k lands alone while k+1 is still in flight
-        half = (p.b1 - p.b0) // 2 if _SPLIT_SLICES and len(streams) > 1 else 0
-        parts = ([(p.b0, p.b0 + half, 0), (p.b0 + half, p.b1, 1)] if half
-                 else [(p.b0, p.b1, s % len(streams))])
-        evs = []
-        for lo, hi, k in parts:
-            st = streams[k]
-            _native.gpu_memcpy_h2d(data.data_ptr() + lo, ptr + lo, hi - lo,
-                                   st.cuda_stream)
-            ev = torch.cuda.Event()
-            ev.record(st)
-            evs.append(ev)
-        events.append(evs)
-    data.record_stream(streams[0])
-    if len(streams) > 1:
-        data.record_stream(streams[1])
-
-    fields = wire_fields(schema)
-    F = len(fields)
-    streaming = _STREAM_DECODE
-    last_read.update(path="streamed", slices=S, regrows=0)
-    do_scan = streaming and record_type != "ByteArray" and F > 0
-    fuse_crc = verify_crc
-    vals = None
-    if streaming:
-        # one int64 status block, read back whole: [0] broken-chain flag,
-        # [1] fused CRC word (all-ones = clean), [2] the scan's int32 codec
-        # error pair, [3] the extraction's, [4 + j] end of the j-th chain
-        # launch's last candidate (word 4 is the carry into the first: 0)
-        status = torch.zeros(_ST_CARRY + 1 + S, dtype=torch.int64,
-                             device=device)
-        status[_ST_CRC] = -1
-        sp = status.data_ptr()
-        err = status[_ST_ERR:_ST_ERR + 1].view(torch.int32)
-        xerr = status[_ST_XERR:_ST_XERR + 1].view(torch.int32)
-        rows = _StreamRows(n, F if do_scan else 0, device)
-        if do_scan:
-            blob = _schema_blob_device(schema, device)
-            vals = _StreamValues(fields, n, device) if _STREAM_EXTRACT else None
-            meta_dev = torch.empty(F * _native.gpu_devmeta_bytes(),
-                                   dtype=torch.uint8, device=device)
-
-    base = 0    # block_counts offset of the current slice
-    C = 0       # chained candidates so far
-    nchain = 0  # chain launches so far
-    r_done = 0  # records structure-scanned so far
-    pending = None  # the last slice's rows: extracted after the readback
-    avg_bytes = None
-    for s, p in enumerate(plan):
-        for ev in events[s]:
-            main.wait_event(ev)
-        last = s == S - 1
-        nb = nblocks[s]
-        if nb:
-            _native.gpu_frame_scan_count(data.data_ptr(), n, p.scan_lo,
-                                         p.scan_hi, base,
-                                         block_counts.data_ptr(), _stream())
-        if not streaming:
-            base += nb
-            continue
-        if nb:
-            # host syncs below cost nothing while later slices are in flight
-            block_off = excl_sum(block_counts[base:base + nb])
-            c_s = int(block_off[-1].item())
-            base += nb
-            if c_s:
-                rows.reserve(C + c_s, C, r_done, p.scan_hi)
-                _native.gpu_frame_scan_emit(
-                    data.data_ptr(), n, p.scan_lo, p.scan_hi, 0,
-                    block_off.data_ptr(), rows.pos.data_ptr() + C * 8,
-                    rows.lens.data_ptr() + C * 8, _stream())
-                _native.gpu_frame_chain(
-                    rows.pos.data_ptr() + C * 8, rows.lens.data_ptr() + C * 8,
-                    c_s, sp + (_ST_CARRY + nchain) * 8,
-                    sp + (_ST_CARRY + 1 + nchain) * 8,
-                    rows.off.data_ptr() + C * 8, sp + _ST_BROKEN * 8, _stream())
-                nchain += 1
-                C += c_s
-        if not do_scan or C == r_done:
-            continue
-        if last:
-            # every candidate ends inside the file (the COUNT cull), so all
-            # of them have arrived; the chain flag rides the final readback
-            avail = C
-            end = n
-        else:
-            st_h = status.cpu()
-            if int(st_h[_ST_BROKEN]) != 0:
-                streaming = do_scan = False  # finish the COUNT passes only
-                continue
-            end = int(st_h[_ST_CARRY + nchain])
-            avail = stream_plan.arrived_records(C, end, p.b1)
-            if avail < C:
-                end = p.b1
-        if avail > r_done:
-            if avg_bytes is None:  # wave/lane choice: once per file
-                avg_bytes = max(0, end // avail - 16)
-            _native.gpu_scan_records(
-                data.data_ptr(), rows.off.data_ptr() + r_done * 8,
-                rows.lens.data_ptr() + r_done * 8, avail - r_done,
-                FMT[record_type], blob.data_ptr(), F,
-                rows.stats.data_ptr() + r_done * F * 48, err.data_ptr(),
-                sp + _ST_CRC * 8 if fuse_crc else 0, _stream(), avg_bytes,
-                rec_base=r_done, max_blocks=0 if last else _STREAM_MAX_BLOCKS)
-            if vals is not None:
-                rows.scan_stats(r_done, avail)
-                if last:
-                    pending = (r_done, avail)
-                elif vals.ok:
-                    # running totals + error words of the rows scanned so
-                    # far: extraction only ever sees rows that scanned clean
-                    h = torch.cat(rows.totals(avail)
-                                  + [status[:_ST_CARRY]]).cpu()
-                    pair = h[3 * F + _ST_ERR:3 * F + _ST_ERR + 1].view(torch.int32)
-                    if int(h[3 * F + _ST_CRC]) != -1 or int(pair[0]) != 0:
-                        vals.ok = False  # keep scanning; raised at the end
-                    else:
-                        vals.extract(data, rows, r_done, avail,
-                                     h[:3 * F].view(3, F), end, meta_dev,
-                                     xerr, avg_bytes,
-                                     _STREAM_MAX_BLOCKS)
-            r_done = avail
-
-    def unstreamed():
-        last_read["path"] = "fallback" if _STREAM_DECODE else "unstreamed"
-        ranges = [(p.scan_lo, p.scan_hi) for p in plan if p.scan_hi > p.scan_lo]
-        off, lens, _ = _emit_and_chain(data, ranges, block_counts, n)
-        return decode_device(data, off, lens, schema, record_type, verify_crc)
-
-    if not streaming or C == 0:
-        return unstreamed()
-    R = C
-    if not do_scan:
-        st_h = status.cpu()
-        if int(st_h[_ST_BROKEN]) != 0 or int(st_h[_ST_CARRY + nchain]) != n:
-            return unstreamed()
-        return decode_device(data, rows.off[:R], rows.lens[:R], schema,
-                             record_type, verify_crc)
-
-    stats = rows.stats[:R]
-    if vals is None:
-        rows.scan_stats(0, R)
-    # ONE packed readback: totals, then the status block
-    packed = torch.cat(rows.totals(R) + [status]).cpu()
-    st_h = packed[3 * F:]
-    if int(st_h[_ST_BROKEN]) != 0 or int(st_h[_ST_CARRY + nchain]) != n:
-        return unstreamed()
-    pair = st_h[_ST_ERR:_ST_ERR + 1].view(torch.int32)
-    _raise_scan_errors(int(st_h[_ST_CRC]) if fuse_crc else -1, int(pair[0]),
-                       int(pair[1]))
-    totals_h = packed[:3 * F].view(3, F)
-    val_base, byte_base, list_base = rows.planes
-    if vals is None:
-        cols = _extract_columns(data, R, fields, stats,
-                                val_base[:, :R + 1], byte_base[:, :R + 1],
-                                list_base[:, :R + 1], totals_h, xerr,
-                                max(0, n // R - 16))
-    else:
-        # everything before the last slice's rows was extracted under the DMA
-        if not vals.ok:
-            raise RuntimeError("streamed decode: scan error lost")
-        if pending is not None:
-            vals.extract(data, rows, pending[0], pending[1], totals_h, n,
-                         meta_dev, xerr, avg_bytes, 0)
-        cols = vals.columns(stats, val_base, list_base, R)
-    err_h = xerr.cpu()
-    if int(err_h[0]) != 0:
-        _raise_extract_error(int(err_h[0]), int(err_h[1]))
-    return RecordBatch(schema, cols, R)
-
-
 # words of the streamed read's status block
 _ST_BROKEN, _ST_CRC, _ST_ERR, _ST_XERR, _ST_CARRY = 0, 1, 2, 3, 4
+
+
+class _StreamStatus:
+    """One int64 status block per streamed read, read back whole: the
+    broken-chain flag, the fused CRC word (all-ones = clean), the scan's
+    int32 codec error pair, the extraction's, then one word per chain
+    launch: word k is the end of the k-th launch's last candidate and the
+    carry into the next (the carry into the first is 0)."""
+
+    def __init__(self, max_chains: int, device):
+        self.words = torch.zeros(_ST_CARRY + 1 + max_chains, dtype=torch.int64,
+                                 device=device)
+        self.words[_ST_CRC] = -1
+        self.err = self.words[_ST_ERR:_ST_ERR + 1].view(torch.int32)
+        self.xerr = self.words[_ST_XERR:_ST_XERR + 1].view(torch.int32)
+
+    def addr(self, word: int) -> int:
+        return self.words.data_ptr() + word * 8
+
+    def carry_addr(self, k: int) -> int:
+        """Carry into chain launch k == end of launch k - 1."""
+        return self.addr(_ST_CARRY + k)
+
+    def head(self) -> torch.Tensor:
+        """The words before the carries: all that scan_error() reads."""
+        return self.words[:_ST_CARRY]
+
+    # decoding a host copy of the block (or of its head)
+    @staticmethod
+    def chain_end(h, nchain: int) -> Optional[int]:
+        """End of the chain after nchain launches; None once it broke."""
+        return None if int(h[_ST_BROKEN]) != 0 else int(h[_ST_CARRY + nchain])
+
+    @staticmethod
+    def scan_error(h):
+        """(crc word, codec rc, 1 + offending record) of the rows scanned."""
+        pair = h[_ST_ERR:_ST_ERR + 1].view(torch.int32)
+        return int(h[_ST_CRC]), int(pair[0]), int(pair[1])
 
 
 class _StreamRows:
@@ -992,6 +831,16 @@ class _StreamRows:
                 torch.empty(cap, **i64),
                 torch.empty((cap, self.F, 6), **i64) if self.F else None,
                 planes)
+
+    def cand_ptrs(self, c: int):
+        """Addresses of candidate c's (pos, len, off) entries."""
+        return (self.pos.data_ptr() + c * 8, self.lens.data_ptr() + c * 8,
+                self.off.data_ptr() + c * 8)
+
+    def row_ptrs(self, r: int):
+        """Addresses of record r's (off, len, FieldStat row) entries."""
+        return (self.off.data_ptr() + r * 8, self.lens.data_ptr() + r * 8,
+                self.stats.data_ptr() + r * self.F * 48)
 
     def scan_stats(self, r0: int, r1: int):
         """Ranged stat prefix sums over scanned rows [r0, r1): carries on
@@ -1030,103 +879,260 @@ class _StreamRows:
         self.cap = cap
 
 
-class _StreamValues:
-    """Output buffers of the streamed extraction, per field: values (int64
-    or float32), payload bytes, elem_len and sub_count. Sized like the row
-    buffers — density of the first extracted range times _STREAM_HEADROOM —
-    and regrown by copying the filled prefix; extract() checks every
-    capacity against the host-read running totals before it launches."""
+class _StreamedRead:
+    """State and steps of one streamed read over `data`, whose slices are
+    still landing. Per slice, in order: discover() its candidates, arrived()
+    decides how many records lie inside the bytes that have landed, scan()
+    decodes them; finish() runs after the last slice."""
 
-    _DIMS = (("i64_vals", 0), ("f32_vals", 0), ("elem_len", 0),
-             ("bytes_data", 1), ("sub_count", 2))
+    def __init__(self, data: torch.Tensor, nslices: int, schema: StructType,
+                 record_type: str, verify_crc: bool):
+        device = data.device
+        self.data = data
+        self.n = data.numel()
+        self.schema = schema
+        self.record_type = record_type
+        self.verify_crc = verify_crc
+        fields = wire_fields(schema)
+        F = self.F = len(fields)
+        # ByteArray and field-less schemas only stream the frame discovery
+        self.do_scan = record_type != "ByteArray" and F > 0
+        self.status = _StreamStatus(nslices, device)
+        self.rows = _StreamRows(self.n, F if self.do_scan else 0, device)
+        if self.do_scan:
+            self.blob = _schema_blob_device(schema, device)
+            self.vals = _FieldValues(fields, self.n, device)
+            self.meta_dev = torch.empty(F * _native.gpu_devmeta_bytes(),
+                                        dtype=torch.uint8, device=device)
+        self.C = 0       # chained candidates so far
+        self.nchain = 0  # chain launches so far
+        self.r_done = 0  # records structure-scanned so far
+        self.x_done = 0  # records extracted so far
+        self.clean = True  # False once a scanned range reported an error
+        self.avg_bytes = None
 
-    def __init__(self, fields, total_bytes: int, device):
-        self.total_bytes = total_bytes
-        self.device = device
-        self.ok = True  # False once a scanned range reported an error
-        self.kinds = [wire_kind_of(f.dataType) for f in fields]
-        self.seqs = [is_sequence_field(f.dataType) for f in fields]
-        self.filled = [[0] * len(fields) for _ in range(3)]
-        self.bufs = []
-        for kind in self.kinds:
-            dt = {"i64_vals": torch.int64, "f32_vals": torch.float32,
-                  "elem_len": torch.int64, "bytes_data": torch.uint8,
-                  "sub_count": torch.int64}
-            self.bufs.append({k: torch.empty(0, dtype=d, device=device)
-                              for k, d in dt.items()})
+    def discover(self, p: stream_plan.SlicePlan, counts: torch.Tensor):
+        """Step 1: prefix-sum the slice's per-block candidate counts, make
+        room, EMIT the candidates behind the earlier ones and chain them on
+        from the previous launch's end."""
+        # host syncs cost nothing while later slices are in flight
+        block_off = excl_sum(counts)
+        c_s = int(block_off[-1].item())
+        if not c_s:
+            return
+        self.rows.reserve(self.C + c_s, self.C, self.r_done, p.scan_hi)
+        pos, lens, off = self.rows.cand_ptrs(self.C)
+        _native.gpu_frame_scan_emit(self.data.data_ptr(), self.n, p.scan_lo,
+                                    p.scan_hi, 0, block_off.data_ptr(), pos,
+                                    lens, _stream())
+        _native.gpu_frame_chain(pos, lens, c_s,
+                                self.status.carry_addr(self.nchain),
+                                self.status.carry_addr(self.nchain + 1), off,
+                                self.status.addr(_ST_BROKEN), _stream())
+        self.nchain += 1
+        self.C += c_s
 
-    def _used(self, i: int, name: str) -> bool:
-        kind = self.kinds[i]
-        return {"i64_vals": kind == KIND_INT64, "f32_vals": kind == KIND_FLOAT,
-                "elem_len": kind == KIND_BYTES}.get(name, True)
+    def arrived(self, p: stream_plan.SlicePlan, last: bool):
+        """Step 2: (records that have fully arrived, bytes they span) once
+        slice p has landed; None when the chain broke."""
+        if not self.do_scan or self.C == self.r_done:
+            return self.r_done, p.b1
+        if last:
+            # every candidate ends inside the file (the COUNT cull), so all
+            # of them have arrived; the chain flag rides the final readback
+            return self.C, self.n
+        end = self.status.chain_end(self.status.words.cpu(), self.nchain)
+        if end is None:
+            return None
+        avail = stream_plan.arrived_records(self.C, end, p.b1)
+        return avail, end if avail == self.C else p.b1
 
-    def _reserve(self, totals, bytes_seen: int):
-        for i, bufs in enumerate(self.bufs):
-            for name, dim in self._DIMS:
-                if not self._used(i, name):
-                    continue
-                need = int(totals[dim][i])
-                old = bufs[name]
-                cap = stream_plan.grown_capacity(
-                    old.numel(), need, bytes_seen, self.total_bytes,
-                    _STREAM_HEADROOM, min_unit=1)
-                if cap == old.numel():
-                    continue
-                new = torch.empty(cap, dtype=old.dtype, device=self.device)
-                k = self.filled[dim][i]
-                if k:
-                    new[:k].copy_(old[:k])
-                if old.numel():
-                    last_read["regrows"] = last_read.get("regrows", 0) + 1
-                bufs[name] = new
+    def scan(self, avail: int, end: int, last: bool):
+        """Step 3: structure-scan (+CRC) records [r_done, avail), extend the
+        stat prefix sums over them and, under the later slices' DMA, extract
+        their values. The last slice's rows wait for finish()."""
+        r0 = self.r_done
+        if avail <= r0:
+            return
+        if self.avg_bytes is None:  # wave/lane choice: once per file
+            self.avg_bytes = max(0, end // avail - 16)
+        off, lens, stats = self.rows.row_ptrs(r0)
+        _native.gpu_scan_records(
+            self.data.data_ptr(), off, lens, avail - r0, FMT[self.record_type],
+            self.blob.data_ptr(), self.F, stats, self.status.err.data_ptr(),
+            self.status.addr(_ST_CRC) if self.verify_crc else 0, _stream(),
+            self.avg_bytes, rec_base=r0)
+        self.rows.scan_stats(r0, avail)
+        self.r_done = avail
+        if not _STREAM_EXTRACT or last or not self.clean:
+            return
+        # running totals + error words of the rows scanned so far:
+        # extraction only ever sees rows that scanned clean
+        F = self.F
+        h = torch.cat(self.rows.totals(avail) + [self.status.head()]).cpu()
+        crc_bad, rc, _ = self.status.scan_error(h[3 * F:])
+        if crc_bad != -1 or rc != 0:
+            self.clean = False  # keep scanning; raised at the end
+            return
+        self._extract(avail, h[:3 * F].view(3, F), end)
 
-    def extract(self, data, rows, r0: int, r1: int, totals, bytes_seen: int,
-                meta_dev, xerr, avg_bytes: int, max_blocks: int):
-        """Extract records [r0, r1). totals ([3][F], host) are the running
-        totals after row r1: every buffer is grown to hold them first."""
-        self._reserve(totals, bytes_seen)
-        v, b, l = rows.planes
-        metas = []
-        for i, bufs in enumerate(self.bufs):
-            metas.append({
-                "kind": self.kinds[i], "is_seq": 1 if self.seqs[i] else 0,
-                "i64_vals": bufs["i64_vals"].data_ptr(),
-                "f32_vals": bufs["f32_vals"].data_ptr(),
-                "bytes_data": bufs["bytes_data"].data_ptr(),
-                "elem_len": bufs["elem_len"].data_ptr(),
-                "sub_count": bufs["sub_count"].data_ptr(),
-                "val_base": v[i].data_ptr(),
-                "byte_base": b[i].data_ptr(),
-                "list_base": l[i].data_ptr() if self.seqs[i] else 0,
-            })
-        _native.gpu_extract_fields(data.data_ptr(), r1 - r0, len(self.bufs),
-                                   rows.stats.data_ptr(), metas,
-                                   meta_dev.data_ptr(), xerr.data_ptr(),
-                                   _stream(), avg_bytes, r0=r0,
-                                   max_blocks=max_blocks)
-        self.filled = [[int(totals[d][i]) for i in range(len(self.bufs))]
-                       for d in range(3)]
+    def _extract(self, r1: int, totals_h, bytes_seen: int):
+        self.vals.extract(self.data, self.rows.stats, self.rows.planes,
+                          self.x_done, r1, totals_h, bytes_seen, self.meta_dev,
+                          self.status.xerr, self.avg_bytes)
+        self.x_done = r1
 
-    def columns(self, stats, val_base, list_base, R: int) -> List[WireColumn]:
-        cols = []
-        for i, bufs in enumerate(self.bufs):
-            kind, seq = self.kinds[i], self.seqs[i]
-            nv, nb, nl = (self.filled[d][i] for d in range(3))
-            presence = (stats[:, i, 0] >= 0).to(torch.uint8)
-            elem_off = None
-            if kind == KIND_BYTES:
-                elem_off = excl_sum(bufs["elem_len"][:nv])
-            sub_off = None
-            if seq:
-                sub_off = excl_sum(bufs["sub_count"][:nl])
-            values = (bufs["i64_vals"][:nv] if kind == KIND_INT64 else
-                      bufs["f32_vals"][:nv] if kind == KIND_FLOAT else
-                      bufs["bytes_data"][:nb])
-            cols.append(WireColumn(kind, seq, presence, val_base[i][:R + 1],
-                                   values, elem_off,
-                                   list_base[i][:R + 1] if seq else None,
-                                   sub_off))
-        return cols
+    def finish(self) -> Optional[RecordBatch]:
+        """Step 4, after the last slice: one packed readback, the errors in
+        decode_device's order, the rows not yet extracted, the columns. None
+        when the chain did not hold over the whole file."""
+        R, F, n = self.C, self.F, self.n
+        if R == 0:
+            return None
+        if not self.do_scan:
+            if self.status.chain_end(self.status.words.cpu(), self.nchain) != n:
+                return None
+            return decode_device(self.data, self.rows.off[:R],
+                                 self.rows.lens[:R], self.schema,
+                                 self.record_type, self.verify_crc)
+        # ONE packed readback: totals, then the status block
+        packed = torch.cat(self.rows.totals(R) + [self.status.words]).cpu()
+        st_h = packed[3 * F:]
+        if self.status.chain_end(st_h, self.nchain) != n:
+            return None
+        crc_bad, rc, rec1 = self.status.scan_error(st_h)
+        _raise_scan_errors(crc_bad if self.verify_crc else -1, rc, rec1)
+        if not self.clean:
+            raise RuntimeError("streamed decode: scan error lost")
+        if self.x_done < R:
+            self._extract(R, packed[:3 * F].view(3, F), n)
+        val_base, _, list_base = self.rows.planes
+        cols = self.vals.columns(self.rows.stats[:R], val_base, list_base, R)
+        err_h = self.status.xerr.cpu()
+        if int(err_h[0]) != 0:
+            _raise_extract_error(int(err_h[0]), int(err_h[1]))
+        return RecordBatch(self.schema, cols, R)
+
+
+def _issue_h2d_slices(data: torch.Tensor, ptr: int, plan) -> list:
+    """Issue ALL H2D slices up front on the side streams. Returns one list
+    of events per slice: the main stream gates each slice's work on just
+    that slice's copies."""
+    main = torch.cuda.current_stream()
+    streams = _dma_streams()
+    for st in streams:
+        st.wait_stream(main)  # `data` allocation ordering
+    events = []
+    for s, p in enumerate(plan):
+        # each slice goes half on either DMA stream: the streams share the
+        # link, so whole slices alternating between them land in PAIRS;
+        # split, slice k lands alone while k+1 is still in flight
+        half = (p.b1 - p.b0) // 2 if _SPLIT_SLICES and len(streams) > 1 else 0
+        parts = ([(p.b0, p.b0 + half, 0), (p.b0 + half, p.b1, 1)] if half
+                 else [(p.b0, p.b1, s % len(streams))])
+        evs = []
+        for lo, hi, k in parts:
+            st = streams[k]
+            _native.gpu_memcpy_h2d(data.data_ptr() + lo, ptr + lo, hi - lo,
+                                   st.cuda_stream)
+            ev = torch.cuda.Event()
+            ev.record(st)
+            evs.append(ev)
+        events.append(evs)
+    for st in streams:
+        data.record_stream(st)
+    return events
+
+
+def _scan_blocks(p: stream_plan.SlicePlan) -> int:
+    """Frame-scan blocks (== block_counts entries) of slice p's scan range."""
+    if p.scan_hi <= p.scan_lo:
+        return 0
+    return int(_native.gpu_frame_scan_blocks(p.scan_lo, p.scan_hi))
+
+
+def _count_slice(data, p, evs, block_counts, base: int) -> int:
+    """Once slice p's copies (events evs) have landed: the COUNT pass over
+    its scan range into block_counts[base:]. Returns its block count."""
+    main = torch.cuda.current_stream()
+    for ev in evs:
+        main.wait_event(ev)
+    nb = _scan_blocks(p)
+    if nb:
+        _native.gpu_frame_scan_count(data.data_ptr(), data.numel(), p.scan_lo,
+                                     p.scan_hi, base, block_counts.data_ptr(),
+                                     _stream())
+    return nb
+
+
+def _read_unstreamed(data, plan, block_counts, events, first: int,
+                     schema: StructType, record_type: str,
+                     verify_crc: bool) -> RecordBatch:
+    """The unstreamed read: COUNT under the DMA for the slices from `first`
+    on (the earlier ones have been counted), then the whole-file
+    _emit_and_chain + decode_device. TFREC_STREAM_DECODE=0 starts here with
+    first == 0; the streamed loop leaves through here on a broken chain."""
+    last_read["path"] = "fallback" if _STREAM_DECODE else "unstreamed"
+    base = sum(_scan_blocks(p) for p in plan[:first])
+    for p, evs in zip(plan[first:], events[first:]):
+        base += _count_slice(data, p, evs, block_counts, base)
+    ranges = [(p.scan_lo, p.scan_hi) for p in plan if p.scan_hi > p.scan_lo]
+    off, lens, _ = _emit_and_chain(data, ranges, block_counts, data.numel())
+    return decode_device(data, off, lens, schema, record_type, verify_crc)
+
+
+def read_file_to_batch_pipelined(path: str, schema: StructType, record_type: str,
+                                 verify_crc: bool = True,
+                                 device="cuda") -> RecordBatch:
+    """File -> device batch with the H2D DMA sliced so the work on slice k
+    runs while slice k+1 is still in flight: frame discovery (COUNT, prefix
+    sum, EMIT), the chain check, the fused structure scan + CRC, the stat
+    prefix sums and the extraction of the records that have fully arrived.
+    Positions within 32 bytes of a slice boundary are deferred to the next
+    slice's launch (their load window extends past the boundary). After the
+    last slice only that slice's work remains. A broken frame chain abandons
+    the streamed attempt for _read_unstreamed, which is also what
+    TFREC_STREAM_DECODE=0 runs."""
+    check_native()
+    n = os.path.getsize(path)
+    if n == 0:
+        z = torch.zeros(0, dtype=torch.int64, device=device)
+        return decode_device(torch.zeros(0, dtype=torch.uint8, device=device),
+                             z, z.clone(), schema, record_type, verify_crc)
+    ptr, pinned = _native.file_mmap_pinned(path, n, False)
+    if not pinned:
+        data = _read_file_staged(path, torch.empty(n, dtype=torch.uint8,
+                                                   device=device))
+        off, lens = scan_frames_device(data)
+        return decode_device(data, off, lens, schema, record_type, verify_crc)
+    data = torch.empty(n, dtype=torch.uint8, device=device)
+    plan = stream_plan.plan_slices(n, _READ_SLICE)
+    S = len(plan)
+    # pre-size the per-block count buffer over the slice scan ranges
+    block_counts = torch.empty(max(sum(_scan_blocks(p) for p in plan), 1),
+                               dtype=torch.int64, device=data.device)
+    events = _issue_h2d_slices(data, ptr, plan)
+    last_read.update(path="streamed", slices=S, regrows=0)
+    unstreamed = (data, plan, block_counts, events)
+    decode = (schema, record_type, verify_crc)
+    if not _STREAM_DECODE:
+        return _read_unstreamed(*unstreamed, 0, *decode)
+
+    rd = _StreamedRead(data, S, *decode)
+    base = 0  # block_counts offset of the current slice
+    for s, p in enumerate(plan):
+        nb = _count_slice(data, p, events[s], block_counts, base)
+        if nb:
+            rd.discover(p, block_counts[base:base + nb])
+            base += nb
+        got = rd.arrived(p, last=s == S - 1)
+        if got is None:
+            return _read_unstreamed(*unstreamed, s + 1, *decode)
+        rd.scan(*got, last=s == S - 1)
+    batch = rd.finish()
+    if batch is None:
+        return _read_unstreamed(*unstreamed, S, *decode)
+    return batch
 
 
 def gz_device_meta(path: str):
@@ -1148,9 +1154,7 @@ def _device_inflate_group(data: torch.Tensor, gz_items, device) -> bool:
     the caller redoes those files on host zlib. The gzip CRC32 trailer is
     NOT checked here: the TFRecord layer CRC32C-verifies every record of the
     inflated bytes (a corrupt stream also breaks the frame chain)."""
-    import os as _os
-
-    comp_sizes = [_os.path.getsize(p) for p, _, _ in gz_items]
+    comp_sizes = [os.path.getsize(p) for p, _, _ in gz_items]
     comp_total = sum(comp_sizes)
     comp = torch.empty(max(comp_total, 1), dtype=torch.uint8,
                        device=device)[:comp_total]
@@ -1192,7 +1196,7 @@ def _device_inflate_group(data: torch.Tensor, gz_items, device) -> bool:
     # heavy segments favor the whole-wave kernel (wide cooperative copies,
     # no divergence between halves). TFREC_INFLATE_STREAMS=1|2 forces one.
     meta_np = np.array([in_off, in_len, out_off, out_len], np.int64)
-    force = _os.environ.get("TFREC_INFLATE_STREAMS", "")
+    force = os.environ.get("TFREC_INFLATE_STREAMS", "")
     spw_lit = 2
     if force in ("1", "2", "4"):
         spw_lit = int(force)
@@ -1243,8 +1247,6 @@ def read_files_to_batch(paths, schema: StructType, record_type: str,
     our segment table are inflated by the device inflater (all files'
     segments in one launch). Returns (device RecordBatch, np.ndarray
     row_counts per file)."""
-    import os as _os
-
     from ..io import paths as P
 
     check_native()
@@ -1260,7 +1262,7 @@ def read_files_to_batch(paths, schema: StructType, record_type: str,
             sizes.append(sum(u for _, u in meta[1]))
         else:
             metas.append(None)
-            sizes.append(_os.path.getsize(p))
+            sizes.append(os.path.getsize(p))
     n = sum(sizes)
     if n == 0:
         if schema is None:
@@ -1348,15 +1350,7 @@ def encode_partitions_device(batch: RecordBatch, part_codes: np.ndarray,
     check_native()
     R = batch.num_rows
     device = batch.columns[0].presence.device if batch.columns else torch.device("cuda")
-    blob = torch.frombuffer(bytearray(schema_blob(batch.schema)),
-                            dtype=torch.uint8).to(device)
-    col_dicts = [_col_ptrs(c) for c in batch.columns]
-    cols_dev = torch.empty(_native.gpu_devcols_bytes(len(col_dicts)),
-                           dtype=torch.uint8, device=device)
-    psize = torch.empty(R, dtype=torch.int64, device=device)
-    _native.gpu_size_records(col_dicts, cols_dev.data_ptr(), blob.data_ptr(),
-                             FMT[record_type], R, psize.data_ptr(), _stream())
-    frame_off = excl_sum(psize)
+    cols_dev, blob, psize, frame_off = _size_records(batch, record_type, device)
     total = int(frame_off[-1].item())
     file = torch.empty(total, dtype=torch.uint8, device=device)
     err = torch.zeros(2, dtype=torch.int32, device=device)

@@ -158,10 +158,32 @@ def _assert_same(got, want):
                     (f.name, part)
 
 
+def _assert_matches_host_codec(want, img, schema, record_type, verify_crc):
+    """The oracle shares its extraction and column assembly with the code
+    under test, so it is itself anchored to the host codec."""
+    host = cpu_engine.decode_buffer(np.frombuffer(img, np.uint8), schema,
+                                    record_type, verify_crc)
+    dev = _g().batch_to_host(want)
+    assert dev.num_rows == host.num_rows
+    assert len(dev.columns) == len(host.columns)
+    for f, a, b in zip(schema.fields, dev.columns, host.columns):
+        for part in PARTS:
+            va, vb = getattr(a, part), getattr(b, part)
+            assert (va is None) == (vb is None), (f.name, part)
+            if vb is not None:
+                assert np.array_equal(np.asarray(va), np.asarray(vb)), \
+                    (f.name, part)
+
+
 def _check(tmp_path, monkeypatch, case, read_slice, verify_crc, extract,
            path="streamed", min_slices=1):
     img, schema, record_type = case
     want = _oracle(img, schema, record_type, verify_crc)
+    # The empty file stays un-anchored: decode_device's empty batch carries no
+    # elem_off where the host codec returns [0] (a difference older than
+    # this check).
+    if not isinstance(want, tuple) and img:
+        _assert_matches_host_codec(want, img, schema, record_type, verify_crc)
     got = _streamed(tmp_path, monkeypatch, img, schema, record_type,
                     verify_crc, read_slice, extract)
     _assert_same(got, want)
@@ -207,6 +229,27 @@ def test_forced_unstreamed_path(tmp_path, monkeypatch):
     monkeypatch.setattr(g, "_READ_SLICE", 8 << 10)
     _assert_same(g.read_file_to_batch_pipelined(path, schema, rt), want)
     assert g.last_read["path"] == "unstreamed"
+
+
+def test_whole_file_decode_allocates_exactly():
+    # decode_device knows every total before it allocates: the growable value
+    # buffers it shares with the streamed read must not add headroom there
+    import torch
+    g = _g()
+    img, schema, rt = _flagship()
+    data = torch.frombuffer(bytearray(img), dtype=torch.uint8).cuda()
+    off, lens = g.scan_frames_device(data)
+    batch = g.decode_device(data, off, lens, schema, rt, True)
+    assert batch.num_rows == 300
+    checked = 0
+    for f, c in zip(schema.fields, batch.columns):
+        for part in ("values", "elem_off", "sub_off"):
+            t = getattr(c, part)
+            if t is not None:
+                assert t.untyped_storage().nbytes() == \
+                    t.numel() * t.element_size(), (f.name, part)
+                checked += 1
+    assert checked >= len(batch.columns)
 
 
 @crc
@@ -391,18 +434,25 @@ def test_truncated_mid_record(tmp_path, monkeypatch, verify_crc, extract):
 
 @crc
 @ext
+@pytest.mark.parametrize("at", [2, 120, 199])
 def test_false_positive_header_falls_back(tmp_path, monkeypatch, verify_crc,
-                                          extract):
+                                          extract, at):
     # a bytes value that embeds a complete, valid frame header (length plus
     # masked length CRC): frame discovery reports it as a candidate, the
-    # chain check rejects it, and the whole-file path stitches it out
+    # chain check rejects it, and the whole-file path stitches it out. The
+    # file is three 4 KiB slices long and record `at` puts the fake header in
+    # the first, the middle and the last of them: the streamed loop leaves
+    # for the fallback from its first slice, mid-loop and at the end.
     from spark_tfrecord_amd import _native
     head = struct.pack("<Q", 5)
     fake = head + struct.pack("<I", _native.masked_crc32c(head)) + b"y" * 40
     schema = stf.StructType([stf.StructField("b", stf.BinaryType(), True)])
     vals = [b"z" * (i % 50) for i in range(200)]
-    vals[120] = fake
+    vals[at] = fake
     img = cpu_engine.encode_batch(_batch(schema, {"b": vals}), "Example")
+    off, _ = _frame_bounds(img)
+    assert len(img) > 2 * 4096 and len(img) <= 3 * 4096
+    assert int(off[at]) // 4096 == {2: 0, 120: 1, 199: 2}[at]
     want = _check(tmp_path, monkeypatch, (img, schema, "Example"), 4 << 10,
                   verify_crc, extract, path="fallback")
     assert want.num_rows == 200
