@@ -890,8 +890,16 @@ struct DecodeDst {
   i64* sub_count;   // per-sub-list value count (seq), later prefix-summed
 };
 
+// The extraction functions below take OFFS: false (the host decoder) stores
+// lengths and counts as described above; true (the device kernels) stores the
+// finished offset columns through the same two pointers instead: the
+// string's starting byte offset in elem_len[vi] and the sub-list's starting
+// value slot in sub_count[li]. Both cursors start from the row's absolute
+// bases, so these are the exclusive prefix sums of the lengths and counts.
+
 // Extracts one list body's values. Cursors are advanced versions of the
 // pass-A counters: *vi = next value slot, *bi = next byte offset.
+template <bool OFFS = false>
 TFR_HOSTDEV inline int32_t extract_list_body(const u8* p, const u8* end, int32_t kind,
                                              const DecodeDst& dst, i64* vi, i64* bi) {
   while (p < end) {
@@ -919,7 +927,7 @@ TFR_HOSTDEV inline int32_t extract_list_body(const u8* p, const u8* end, int32_t
         __builtin_memcpy(d + i, &w, 8);
       }
       for (; i < len; ++i) d[i] = p[i];
-      dst.elem_len[*vi] = static_cast<i64>(len);
+      dst.elem_len[*vi] = OFFS ? *bi : static_cast<i64>(len);
       *bi += static_cast<i64>(len);
       *vi += 1;
       p += len;
@@ -964,6 +972,7 @@ TFR_HOSTDEV inline int32_t extract_list_body(const u8* p, const u8* end, int32_t
   return ERR_OK;
 }
 
+template <bool OFFS = false>
 TFR_HOSTDEV inline int32_t extract_feature_body(const u8* p, const u8* end,
                                                 int32_t kind, const DecodeDst& dst,
                                                 i64* vi, i64* bi) {
@@ -977,7 +986,7 @@ TFR_HOSTDEV inline int32_t extract_feature_body(const u8* p, const u8* end,
       u64 len;
       p = read_varint(p, end, &len);
       if (!p || static_cast<u64>(end - p) < len) return ERR_TRUNCATED;
-      int32_t rc = extract_list_body(p, p + len, kind, dst, vi, bi);
+      int32_t rc = extract_list_body<OFFS>(p, p + len, kind, dst, vi, bi);
       if (rc != ERR_OK) return rc;
       p += len;
     } else {
@@ -991,6 +1000,7 @@ TFR_HOSTDEV inline int32_t extract_feature_body(const u8* p, const u8* end,
 // Pass B for one (record, field): body extent [pos, pos+len) from pass A.
 // val_base / byte_base / list_base are this row's starting slots from the
 // prefix sums. For seq fields, also emits per-sub-list counts.
+template <bool OFFS = false>
 TFR_HOSTDEV inline int32_t extract_field(const u8* data, i64 pos, i64 len,
                                          int32_t kind, int32_t is_seq,
                                          const DecodeDst& dst, i64 val_base,
@@ -1000,7 +1010,8 @@ TFR_HOSTDEV inline int32_t extract_field(const u8* data, i64 pos, i64 len,
   const u8* end = p + len;
   i64 vi = val_base;
   i64 bi = byte_base;
-  if (!is_seq) return extract_feature_body(p, end, kind, dst, &vi, &bi);
+  if (!is_seq)
+    return extract_feature_body<OFFS>(p, end, kind, dst, &vi, &bi);
   // FeatureList: repeated Feature
   i64 li = list_base;
   while (p < end) {
@@ -1014,9 +1025,9 @@ TFR_HOSTDEV inline int32_t extract_field(const u8* data, i64 pos, i64 len,
       p = read_varint(p, end, &flen);
       if (!p || static_cast<u64>(end - p) < flen) return ERR_TRUNCATED;
       i64 v_before = vi;
-      int32_t rc = extract_feature_body(p, p + flen, kind, dst, &vi, &bi);
+      int32_t rc = extract_feature_body<OFFS>(p, p + flen, kind, dst, &vi, &bi);
       if (rc != ERR_OK) return rc;
-      dst.sub_count[li++] = vi - v_before;
+      dst.sub_count[li++] = OFFS ? v_before : vi - v_before;
       p += flen;
     } else {
       p = skip_field(p, end, wt);

@@ -101,6 +101,11 @@ static_assert(sizeof(FieldStat) == 48, "FieldStat layout shared with Python");
 // the same pass, while the record bytes are L2-hot from the parse — a
 // separate verify kernel costs an extra full-file HBM read and an extra
 // host sync. crc_err[0] stays ~0ULL on success, else 1 + first bad record.
+// gate (optional) is the streamed read's broken-chain word, written by the
+// chain kernels earlier on the stream: when it is set the candidates are
+// not records (a false-positive header may claim the rest of the file, which
+// one lane would then CRC serially), so the launch returns without touching
+// stats. One plain load at kernel start, uniform over the grid.
 __global__ void scan_records_kernel(const u8* __restrict__ data,
                                     const i64* __restrict__ off,
                                     const i64* __restrict__ len, i64 R, int32_t fmt,
@@ -108,8 +113,9 @@ __global__ void scan_records_kernel(const u8* __restrict__ data,
                                     FieldStat* __restrict__ stats,
                                     int32_t* __restrict__ err,
                                     unsigned long long* crc_err,
-                                    i64 rec_base) {
+                                    i64 rec_base, const i64* gate) {
   __shared__ uint32_t tab[8][256];
+  if (gate && *gate) return;
   if (crc_err) stage_crc_tables(tab);
   SchemaView schema = schema_view(schema_blob);
   for (i64 r = blockIdx.x * (i64)blockDim.x + threadIdx.x; r < R;
@@ -158,19 +164,84 @@ struct DevFieldDst {
   i64* i64_vals;
   float* f32_vals;
   u8* bytes_data;
-  i64* elem_len;
-  i64* sub_count;
+  i64* elem_off;         // [nvals + 1] byte offset of every string + end
+  i64* sub_off;          // [nlists + 1] value slot of every sub-list + end
+  u8* presence;          // row-indexed, 1 where the record has the field
   const i64* val_base;   // [R+1] exclusive scan of nvals
   const i64* byte_base;  // [R+1] exclusive scan of nbytes
   const i64* list_base;  // [R+1] exclusive scan of nlists
+  // capacities in elements, read by extract_gate_kernel only
+  i64 cap_vals;          // i64_vals or f32_vals, whichever the kind fills
+  i64 cap_bytes;
+  i64 cap_elem_off;
+  i64 cap_sub_off;
 };
 
+// The extraction writes finished columns: elem_off / sub_off are the byte
+// and value cursors themselves (absolute, they start from the row's bases),
+// and every launch closes each with its end sentinel, the totals at r_end =
+// r0 + R. A following ranged launch overwrites the sentinels with the same
+// values. No work item writes these slots (they lie one past the last
+// record's values), so block 0 stores them up front, one field per thread:
+// inside the work loop, on the last record's item, the extra live values
+// cost the wave kernel 9 VGPRs (91 -> 100) and with them a wave of
+// occupancy.
+__device__ inline void store_end_sentinels(const DevFieldDst* __restrict__ metas,
+                                           int F, i64 r_end) {
+  if (blockIdx.x != 0) return;
+  for (int f = threadIdx.x; f < F; f += blockDim.x) {
+    const DevFieldDst& m = metas[f];
+    if (m.kind == KIND_BYTES && m.elem_off && m.val_base && m.byte_base)
+      m.elem_off[m.val_base[r_end]] = m.byte_base[r_end];
+    if (m.is_seq && m.sub_off && m.list_base && m.val_base)
+      m.sub_off[m.list_base[r_end]] = m.val_base[r_end];
+  }
+}
+
+// Device-side gate in front of a streamed extraction over rows ending at
+// r_end: one block. Extraction may run only when the chain holds, the fused
+// CRC word is clean, the scan reported no codec error and every field's
+// running totals at r_end (from the three prefix planes) fit its buffers.
+// Writes the verdict (1 = not extracted) to *refused, which the extract
+// kernels load at their start and the host reads with its next snapshot. A
+// kernel of its own because the capacity check is F loads per plane: inside
+// the extract it would repeat in every block.
+__global__ void extract_gate_kernel(const DevFieldDst* __restrict__ metas, int F,
+                                    i64 r_end, const i64* broken,
+                                    const unsigned long long* crc,
+                                    const int32_t* scan_err, i64* refused) {
+  int bad = 0;
+  if (threadIdx.x == 0) {
+    if (broken && *broken) bad = 1;
+    if (crc && *crc != ~0ULL) bad = 1;
+    if (scan_err && scan_err[0] != 0) bad = 1;
+  }
+  for (int f = threadIdx.x; f < F; f += blockDim.x) {
+    const DevFieldDst& m = metas[f];
+    i64 nv = m.val_base ? m.val_base[r_end] : 0;
+    i64 nb = m.byte_base ? m.byte_base[r_end] : 0;
+    i64 nl = m.list_base ? m.list_base[r_end] : 0;
+    if (m.kind == KIND_BYTES) {
+      if (nb > m.cap_bytes || nv + 1 > m.cap_elem_off) bad = 1;
+    } else if (nv > m.cap_vals) {
+      bad = 1;
+    }
+    if (m.is_seq && nl + 1 > m.cap_sub_off) bad = 1;
+  }
+  int any = __syncthreads_or(bad);
+  if (threadIdx.x == 0) *refused = any ? 1 : 0;
+}
+
 // Covers records [r0, r0 + R); stats and the base planes are indexed by the
-// absolute record number.
+// absolute record number. refused (optional) is extract_gate_kernel's
+// verdict: set, nothing is written.
 __global__ void extract_fields_kernel(const u8* __restrict__ data, i64 R, int F,
                                       const FieldStat* __restrict__ stats,
                                       const DevFieldDst* __restrict__ metas,
-                                      int32_t* __restrict__ err, i64 r0) {
+                                      int32_t* __restrict__ err, i64 r0,
+                                      const i64* refused) {
+  if (refused && *refused) return;
+  store_end_sentinels(metas, F, r0 + R);
   i64 total = R * F;
   for (i64 idx = blockIdx.x * (i64)blockDim.x + threadIdx.x; idx < total;
        idx += (i64)gridDim.x * blockDim.x) {
@@ -179,11 +250,12 @@ __global__ void extract_fields_kernel(const u8* __restrict__ data, i64 R, int F,
     i64 r = r0 + q;
     const DevFieldDst& m = metas[f];
     const FieldStat& st = stats[r * F + f];
-    DecodeDst dst{m.i64_vals, m.f32_vals, m.bytes_data, m.elem_len, m.sub_count};
-    int32_t rc = extract_field(data, st.pos, st.len, m.kind, m.is_seq, dst,
-                               m.val_base ? m.val_base[r] : 0,
-                               m.byte_base ? m.byte_base[r] : 0,
-                               m.list_base ? m.list_base[r] : 0);
+    DecodeDst dst{m.i64_vals, m.f32_vals, m.bytes_data, m.elem_off, m.sub_off};
+    if (m.presence) m.presence[r] = st.pos >= 0 ? 1 : 0;
+    int32_t rc = extract_field<true>(data, st.pos, st.len, m.kind, m.is_seq,
+                                     dst, m.val_base ? m.val_base[r] : 0,
+                                     m.byte_base ? m.byte_base[r] : 0,
+                                     m.list_base ? m.list_base[r] : 0);
     if (rc != ERR_OK) set_err(err, rc, r);
   }
 }
@@ -430,7 +502,7 @@ __device__ inline int32_t extract_list_body_wave(const u8* __restrict__ p,
       p = read_varint(p, end, &len);
       if (!p || (u64)(end - p) < len) return ERR_TRUNCATED;
       copy_wave(dst.bytes_data + *bi, p, (i64)len);
-      if (lane == 0) dst.elem_len[*vi] = (i64)len;
+      if (lane == 0) dst.elem_len[*vi] = *bi;  // the finished elem_off
       *bi += (i64)len;
       *vi += 1;
       p += len;
@@ -521,7 +593,7 @@ __device__ inline int32_t extract_field_wave(const u8* __restrict__ data,
       i64 v_before = vi;
       int32_t rc = extract_feature_body_wave(p, p + flen, kind, dst, &vi, &bi);
       if (rc != ERR_OK) return rc;
-      if (lane == 0) dst.sub_count[li] = vi - v_before;
+      if (lane == 0) dst.sub_count[li] = v_before;  // the finished sub_off
       ++li;
       p += flen;
     } else {
@@ -543,8 +615,9 @@ __global__ void scan_records_wave_kernel(const u8* __restrict__ data,
                                          int F, FieldStat* __restrict__ stats,
                                          int32_t* __restrict__ err,
                                          unsigned long long* crc_err,
-                                         i64 rec_base) {
+                                         i64 rec_base, const i64* gate) {
   __shared__ uint32_t tab[8][256];
+  if (gate && *gate) return;
   stage_crc_tables(tab);
   SchemaView schema = schema_view(schema_blob);
   i64 wave = (blockIdx.x * (i64)blockDim.x + threadIdx.x) / 64;
@@ -579,7 +652,10 @@ __global__ void extract_fields_wave_kernel(const u8* __restrict__ data, i64 R,
                                            int F,
                                            const FieldStat* __restrict__ stats,
                                            const DevFieldDst* __restrict__ metas,
-                                           int32_t* __restrict__ err, i64 r0) {
+                                           int32_t* __restrict__ err, i64 r0,
+                                           const i64* refused) {
+  if (refused && *refused) return;
+  store_end_sentinels(metas, F, r0 + R);
   i64 total = R * F;
   i64 wave = (blockIdx.x * (i64)blockDim.x + threadIdx.x) / 64;
   i64 nwaves = ((i64)gridDim.x * blockDim.x) / 64;
@@ -589,12 +665,14 @@ __global__ void extract_fields_wave_kernel(const u8* __restrict__ data, i64 R,
     i64 r = r0 + q;
     const DevFieldDst& m = metas[f];
     const FieldStat& st = stats[r * F + f];
-    DecodeDst dst{m.i64_vals, m.f32_vals, m.bytes_data, m.elem_len, m.sub_count};
+    DecodeDst dst{m.i64_vals, m.f32_vals, m.bytes_data, m.elem_off, m.sub_off};
+    bool lane0 = (threadIdx.x & 63) == 0;
+    if (lane0 && m.presence) m.presence[r] = st.pos >= 0 ? 1 : 0;
     int32_t rc = extract_field_wave(data, st.pos, st.len, m.kind, m.is_seq, dst,
                                     m.val_base ? m.val_base[r] : 0,
                                     m.byte_base ? m.byte_base[r] : 0,
                                     m.list_base ? m.list_base[r] : 0);
-    if (rc != ERR_OK && (threadIdx.x & 63) == 0) set_err(err, rc, r);
+    if (rc != ERR_OK && lane0) set_err(err, rc, r);
   }
 }
 
@@ -964,6 +1042,37 @@ __global__ void frame_chain_kernel(const i64* __restrict__ pos,
   }
 }
 
+// The streamed read's one host round trip per slice: everything the host
+// decides on, packed into one pinned host block by one small block. out[0] =
+// *count (the slice's candidate count, the last element of its block prefix
+// sum; 0 when count is null), out[1 .. nst] = the status block's head words
+// (the extraction gate's verdict among them), out[1 + nst] = *carry (the
+// chain end so far), then the running totals at row r of every field:
+// v[f][r], b[f][r], l[f][r] as three runs of F words (absent when v is null).
+__global__ void stream_snapshot_kernel(const i64* count, const i64* status,
+                                       int nst, const i64* carry, const i64* v,
+                                       const i64* b, const i64* l, i64 stride,
+                                       int F, i64 r, i64* out) {
+  int n = 2 + nst + (v ? 3 * F : 0);
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    i64 x;
+    if (i == 0) {
+      x = count ? *count : 0;
+    } else if (i <= nst) {
+      x = status[i - 1];
+    } else if (i == nst + 1) {
+      x = carry ? *carry : 0;
+    } else {
+      int k = i - (nst + 2);
+      int plane = k / F;
+      int f = k - plane * F;
+      const i64* src = plane == 0 ? v : plane == 1 ? b : l;
+      x = src[(i64)f * stride + r];
+    }
+    out[i] = x;
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Schema inference on device ("per-GPU type-lattice histogram
 // kernel + RCCL all-reduce"). One record per lane walks the Features /
@@ -1263,7 +1372,8 @@ void gpu_crc_verify(uintptr_t data, uintptr_t off, uintptr_t len, i64 R,
 void gpu_scan_records(uintptr_t data, uintptr_t off, uintptr_t len, i64 R,
                       int32_t fmt, uintptr_t schema_blob, int F, uintptr_t stats,
                       uintptr_t err, uintptr_t crc_err, uintptr_t stream,
-                      i64 avg_bytes, i64 rec_base, i64 max_blocks) {
+                      i64 avg_bytes, i64 rec_base, i64 max_blocks,
+                      uintptr_t gate) {
   if (R <= 0) return;
   if (avg_bytes > kWaveRecordBytes) {  // few big records: one per wave
     hipLaunchKernelGGL(scan_records_wave_kernel,
@@ -1271,54 +1381,125 @@ void gpu_scan_records(uintptr_t data, uintptr_t off, uintptr_t len, i64 R,
                        (hipStream_t)stream, (const u8*)data, (const i64*)off,
                        (const i64*)len, R, fmt, (const u8*)schema_blob, F,
                        (FieldStat*)stats, (int32_t*)err,
-                       (unsigned long long*)crc_err, rec_base);
+                       (unsigned long long*)crc_err, rec_base,
+                       (const i64*)gate);
   } else {
     hipLaunchKernelGGL(scan_records_kernel, dim3(grid_for(R, max_blocks)),
                        dim3(kBlock), 0, (hipStream_t)stream, (const u8*)data,
                        (const i64*)off, (const i64*)len, R, fmt,
                        (const u8*)schema_blob, F, (FieldStat*)stats,
-                       (int32_t*)err, (unsigned long long*)crc_err, rec_base);
+                       (int32_t*)err, (unsigned long long*)crc_err, rec_base,
+                       (const i64*)gate);
   }
   HIP_CHECK(hipGetLastError());
 }
 
+// metas: one dict per field with the DevFieldDst members; presence and the
+// cap_* capacities are optional (absent: no presence plane, capacity 0).
+// upload=false skips the table upload: the caller knows meta_dev already
+// holds exactly this table (the pointers only change on a regrow).
+// gate_out != 0 runs the extraction behind extract_gate_kernel, which reads
+// the broken / crc / scan-error words and writes its verdict to gate_out.
 void gpu_extract_fields(uintptr_t data, i64 R, int F, uintptr_t stats,
                         py::list metas, uintptr_t meta_dev, uintptr_t err,
                         uintptr_t stream, i64 avg_bytes, i64 r0,
-                        i64 max_blocks) {
+                        i64 max_blocks, bool upload, uintptr_t gate_broken,
+                        uintptr_t gate_crc, uintptr_t gate_err,
+                        uintptr_t gate_out) {
   if (R <= 0 || F <= 0) return;
-  std::vector<DevFieldDst> host_metas(F);
-  for (int f = 0; f < F; ++f) {
-    py::dict d = metas[f].cast<py::dict>();
-    DevFieldDst& m = host_metas[f];
-    m.kind = d["kind"].cast<int32_t>();
-    m.is_seq = d["is_seq"].cast<int32_t>();
-    m.i64_vals = (i64*)d["i64_vals"].cast<uintptr_t>();
-    m.f32_vals = (float*)d["f32_vals"].cast<uintptr_t>();
-    m.bytes_data = (u8*)d["bytes_data"].cast<uintptr_t>();
-    m.elem_len = (i64*)d["elem_len"].cast<uintptr_t>();
-    m.sub_count = (i64*)d["sub_count"].cast<uintptr_t>();
-    m.val_base = (const i64*)d["val_base"].cast<uintptr_t>();
-    m.byte_base = (const i64*)d["byte_base"].cast<uintptr_t>();
-    m.list_base = (const i64*)d["list_base"].cast<uintptr_t>();
+  if (upload) {
+    std::vector<DevFieldDst> host_metas(F);
+    for (int f = 0; f < F; ++f) {
+      py::dict d = metas[f].cast<py::dict>();
+      auto ptr = [&](const char* k) {
+        return d.contains(k) ? d[k].cast<uintptr_t>() : (uintptr_t)0;
+      };
+      auto cap = [&](const char* k) {
+        return d.contains(k) ? d[k].cast<i64>() : (i64)0;
+      };
+      DevFieldDst& m = host_metas[f];
+      m.kind = d["kind"].cast<int32_t>();
+      m.is_seq = d["is_seq"].cast<int32_t>();
+      m.i64_vals = (i64*)ptr("i64_vals");
+      m.f32_vals = (float*)ptr("f32_vals");
+      m.bytes_data = (u8*)ptr("bytes_data");
+      m.elem_off = (i64*)ptr("elem_off");
+      m.sub_off = (i64*)ptr("sub_off");
+      m.presence = (u8*)ptr("presence");
+      m.val_base = (const i64*)ptr("val_base");
+      m.byte_base = (const i64*)ptr("byte_base");
+      m.list_base = (const i64*)ptr("list_base");
+      m.cap_vals = cap("cap_vals");
+      m.cap_bytes = cap("cap_bytes");
+      m.cap_elem_off = cap("cap_elem_off");
+      m.cap_sub_off = cap("cap_sub_off");
+    }
+    HIP_CHECK(hipMemcpyAsync((void*)meta_dev, host_metas.data(),
+                             sizeof(DevFieldDst) * F, hipMemcpyHostToDevice,
+                             (hipStream_t)stream));
   }
-  HIP_CHECK(hipMemcpyAsync((void*)meta_dev, host_metas.data(),
-                           sizeof(DevFieldDst) * F, hipMemcpyHostToDevice,
-                           (hipStream_t)stream));
+  if (gate_out) {
+    hipLaunchKernelGGL(extract_gate_kernel, dim3(1), dim3(kBlock), 0,
+                       (hipStream_t)stream, (const DevFieldDst*)meta_dev, F,
+                       r0 + R, (const i64*)gate_broken,
+                       (const unsigned long long*)gate_crc,
+                       (const int32_t*)gate_err, (i64*)gate_out);
+  }
   if (avg_bytes > kWaveRecordBytes) {
     hipLaunchKernelGGL(extract_fields_wave_kernel,
                        dim3(grid_for(R * F * 64, max_blocks)), dim3(kBlock), 0,
                        (hipStream_t)stream, (const u8*)data, R, F,
                        (const FieldStat*)stats, (const DevFieldDst*)meta_dev,
-                       (int32_t*)err, r0);
+                       (int32_t*)err, r0, (const i64*)gate_out);
   } else {
     hipLaunchKernelGGL(extract_fields_kernel,
                        dim3(grid_for(R * F, max_blocks)), dim3(kBlock), 0,
                        (hipStream_t)stream, (const u8*)data, R, F,
                        (const FieldStat*)stats, (const DevFieldDst*)meta_dev,
-                       (int32_t*)err, r0);
+                       (int32_t*)err, r0, (const i64*)gate_out);
   }
   HIP_CHECK(hipGetLastError());
+}
+
+// One snapshot of the streamed read's state into the pinned host block
+// out_host (2 + nst + 3F words, see stream_snapshot_kernel), followed by an
+// event on the stream; gpu_stream_snapshot_wait blocks on that event.
+struct SnapshotEvent {
+  int device = -1;
+  hipEvent_t ev = nullptr;
+};
+thread_local SnapshotEvent snapshot_event;
+
+void gpu_stream_snapshot(uintptr_t count, uintptr_t status, int nst,
+                         uintptr_t carry, uintptr_t v, uintptr_t b, uintptr_t l,
+                         i64 stride, int F, i64 r, uintptr_t out_host,
+                         uintptr_t stream) {
+  int dev = 0;
+  HIP_CHECK(hipGetDevice(&dev));
+  SnapshotEvent& se = snapshot_event;
+  if (se.device != dev) {
+    if (se.ev) (void)hipEventDestroy(se.ev);
+    se.ev = nullptr;
+    HIP_CHECK(hipEventCreateWithFlags(&se.ev, hipEventDisableTiming));
+    se.device = dev;
+  }
+  void* out_dev = nullptr;
+  HIP_CHECK(hipHostGetDevicePointer(&out_dev, (void*)out_host, 0));
+  hipLaunchKernelGGL(stream_snapshot_kernel, dim3(1), dim3(kBlock), 0,
+                     (hipStream_t)stream, (const i64*)count,
+                     (const i64*)status, nst, (const i64*)carry, (const i64*)v,
+                     (const i64*)b, (const i64*)l, stride, v ? F : 0, r,
+                     (i64*)out_dev);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipEventRecord(se.ev, (hipStream_t)stream));
+}
+
+void gpu_stream_snapshot_wait() {
+  SnapshotEvent& se = snapshot_event;
+  if (!se.ev)
+    throw std::runtime_error("gpu_stream_snapshot_wait: no snapshot taken");
+  py::gil_scoped_release rel;
+  HIP_CHECK(hipEventSynchronize(se.ev));
 }
 
 size_t gpu_devcols_bytes(int F) { return sizeof(FieldColumn) * (size_t)F; }
@@ -1794,12 +1975,19 @@ void register_gpu(py::module_& m) {
         py::arg("len"), py::arg("R"), py::arg("fmt"), py::arg("schema_blob"),
         py::arg("F"), py::arg("stats"), py::arg("err"), py::arg("crc_err"),
         py::arg("stream"), py::arg("avg_bytes") = 0, py::arg("rec_base") = 0,
-        py::arg("max_blocks") = 0);
+        py::arg("max_blocks") = 0, py::arg("gate") = 0);
   m.def("gpu_extract_fields", &gpu_extract_fields, py::arg("data"),
         py::arg("R"), py::arg("F"), py::arg("stats"), py::arg("metas"),
         py::arg("meta_dev"), py::arg("err"), py::arg("stream"),
         py::arg("avg_bytes") = 0, py::arg("r0") = 0,
-        py::arg("max_blocks") = 0);
+        py::arg("max_blocks") = 0, py::arg("upload") = true,
+        py::arg("gate_broken") = 0, py::arg("gate_crc") = 0,
+        py::arg("gate_err") = 0, py::arg("gate_out") = 0);
+  m.def("gpu_stream_snapshot", &gpu_stream_snapshot, py::arg("count"),
+        py::arg("status"), py::arg("nst"), py::arg("carry"), py::arg("v"),
+        py::arg("b"), py::arg("l"), py::arg("stride"), py::arg("F"),
+        py::arg("r"), py::arg("out_host"), py::arg("stream"));
+  m.def("gpu_stream_snapshot_wait", &gpu_stream_snapshot_wait);
   m.def("gpu_size_records", &gpu_size_records);
   m.def("gpu_emit_records", &gpu_emit_records, py::arg("cols_dev"),
         py::arg("schema_blob"), py::arg("fmt"), py::arg("r0"), py::arg("R"),

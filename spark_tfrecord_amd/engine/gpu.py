@@ -1,9 +1,11 @@
 """GPU engine: gfx950 kernel pipeline orchestration.
 
 Decode: sliced H2D (file-mapping DMA); per arrived slice, under the later
-slices' DMA: two-pass frame scan -> chain check -> fused structure-scan+CRC
--> ranged rocprim prefix sums -> extract_fields -> device wire-form
-columns. decode_device is the same pipeline over a whole resident image.
+slices' DMA and with one host round trip (a snapshot of the device state):
+two-pass frame scan -> chain check -> fused structure-scan+CRC -> ranged
+rocprim prefix sums -> gated extract_fields, which writes the device
+wire-form columns whole (values, elem_off, sub_off, presence).
+decode_device is the same pipeline over a whole resident image.
 Encode: device wire-form -> size_records -> prefix sum -> record-range
 sliced fused emit+CRC overlapped with the D2H DMA into the file mapping.
 
@@ -81,10 +83,11 @@ def pinned_buffer(tag: str, nbytes: int) -> torch.Tensor:
 
 _CHUNK = 64 << 20  # 64 MiB: overlap file IO with PCIe copies chunkwise
 # engine knobs: overridable via env for tuning
-# 32 MiB: the work of the last slice(s) is the decode tail, so smaller
-# slices shorten it until the per-slice host round trips stop fitting under
-# the copies (measured 64/48/32/24/16 MiB: 9.14/8.99/8.84/8.86/9.44 ms per
-# flagship step).
+# 32 MiB: the work of the last slice(s) is the decode tail. With one host
+# round trip per slice the kernel chain of a slice fits under its copy down
+# to 16 MiB, but the step no longer moves with the slice size (measured
+# 32/24/20/16 MiB: 8.50/8.48/8.54/8.52 ms per flagship step, spread 0.09), so
+# the default stays.
 _READ_SLICE = int(os.environ.get("TFREC_READ_SLICE", 32 << 20))
 # Each slice is copied half on either DMA stream. The streams share the
 # link, so whole slices alternating between them land in pairs and the tail
@@ -472,11 +475,12 @@ def decode_device(data: torch.Tensor, off: torch.Tensor, lens: torch.Tensor,
                        int(err[0].item()), int(err[1].item()))
     # every total is known: bytes_seen == total_bytes sizes the buffers exactly
     vals = _FieldValues(fields, data.numel(), device)
-    meta_dev = torch.empty(F * _native.gpu_devmeta_bytes(), dtype=torch.uint8,
-                           device=device)
-    vals.extract(data, stats, (val_base, byte_base, list_base), 0, R, totals_h,
-                 data.numel(), meta_dev, err, avg_bytes)
-    cols = vals.columns(stats, val_base, list_base, R)
+    vals.reserve(totals_h, data.numel())
+    presence = torch.empty((F, R), dtype=torch.uint8, device=device)
+    vals.extract(data, stats, (val_base, byte_base, list_base), presence, 0, R,
+                 _MetaTable(F, device), err, avg_bytes)
+    vals.confirm(totals_h)
+    cols = vals.columns(presence, val_base, list_base, R)
     if int(err[0].item()) != 0:
         _raise_extract_error(int(err[0].item()), int(err[1].item()))
     return RecordBatch(schema, cols, R)
@@ -520,38 +524,60 @@ def _raise_extract_error(rc: int, rec1: int):
                        f"{where} (native error {rc})")
 
 
+class _MetaTable:
+    """Device copy of gpu_extract_fields' field table, uploaded only when it
+    differs from what the device copy last received: the pointers in it only
+    change when a buffer regrows."""
+
+    def __init__(self, F: int, device):
+        self.dev = torch.empty(F * _native.gpu_devmeta_bytes(),
+                               dtype=torch.uint8, device=device)
+        self.last = None
+
+    def changed(self, metas) -> bool:
+        key = [tuple(m.items()) for m in metas]
+        if key == self.last:
+            return False
+        self.last = key
+        return True
+
+
 class _FieldValues:
     """Per-field output buffers of the value extraction: values (int64 or
-    float32), payload bytes, elem_len and sub_count. The one place that
-    builds the metas for gpu_extract_fields and turns filled buffers into
-    WireColumns. extract() grows every buffer to the host-read running
-    totals before it launches: from the value density seen so far times
+    float32), payload bytes and the finished elem_off / sub_off columns. The
+    one place that builds the metas for gpu_extract_fields and turns filled
+    buffers into WireColumns. reserve() grows every buffer to running totals
+    the host has read: from the value density seen so far times
     _STREAM_HEADROOM (a regrow copies the filled prefix), which is exactly
     the totals once bytes_seen == total_bytes, as in decode_device."""
 
     # buffer -> (dtype, the totals row (values, bytes, lists) that sizes it,
-    # the one field kind that fills it; None: every kind)
-    _BUFS = {"i64_vals": (torch.int64, 0, KIND_INT64),
-             "f32_vals": (torch.float32, 0, KIND_FLOAT),
-             "elem_len": (torch.int64, 0, KIND_BYTES),
-             "bytes_data": (torch.uint8, 1, None),
-             "sub_count": (torch.int64, 2, None)}
+    # slots past that total (the offset columns end with a sentinel), the
+    # (kind, is_seq) of the fields that fill it)
+    _BUFS = {"i64_vals": (torch.int64, 0, 0, lambda k, seq: k == KIND_INT64),
+             "f32_vals": (torch.float32, 0, 0, lambda k, seq: k == KIND_FLOAT),
+             "elem_off": (torch.int64, 0, 1, lambda k, seq: k == KIND_BYTES),
+             "bytes_data": (torch.uint8, 1, 0, lambda k, seq: k == KIND_BYTES),
+             "sub_off": (torch.int64, 2, 1, lambda k, seq: seq)}
 
     def __init__(self, fields, total_bytes: int, device):
         self.total_bytes = total_bytes
         self.device = device
         self.kinds = [wire_kind_of(f.dataType) for f in fields]
         self.seqs = [is_sequence_field(f.dataType) for f in fields]
+        # running totals [3][F] of the rows whose extraction is confirmed
         self.filled = [[0] * len(fields) for _ in range(3)]
         self.bufs = [{k: torch.empty(0, dtype=d, device=device)
-                      for k, (d, _, _) in self._BUFS.items()} for _ in fields]
+                      for k, (d, _, _, _) in self._BUFS.items()} for _ in fields]
 
-    def _reserve(self, totals, bytes_seen: int):
+    def reserve(self, totals, bytes_seen: int):
+        """Room for the running totals ([3][F], host) seen bytes_seen bytes
+        into the file."""
         for i, bufs in enumerate(self.bufs):
-            for name, (_, dim, kind) in self._BUFS.items():
-                if kind not in (None, self.kinds[i]):
+            for name, (_, dim, extra, fills) in self._BUFS.items():
+                if not fills(self.kinds[i], self.seqs[i]):
                     continue
-                need = int(totals[dim][i])
+                need = int(totals[dim][i]) + extra
                 old = bufs[name]
                 cap = stream_plan.grown_capacity(
                     old.numel(), need, bytes_seen, self.total_bytes,
@@ -559,57 +585,67 @@ class _FieldValues:
                 if cap == old.numel():
                     continue
                 new = torch.empty(cap, dtype=old.dtype, device=self.device)
-                k = self.filled[dim][i]
+                k = min(self.filled[dim][i] + extra, old.numel())
                 if k:
                     new[:k].copy_(old[:k])
                 if old.numel():
                     last_read["regrows"] = last_read.get("regrows", 0) + 1
                 bufs[name] = new
 
-    def extract(self, data, stats, planes, r0: int, r1: int, totals,
-                bytes_seen: int, meta_dev, err, avg_bytes: int):
-        """Extract records [r0, r1). stats is the FieldStat tensor from row
-        0, planes the three [F][stride] prefix-sum planes; totals ([3][F],
-        host) are the running totals after row r1."""
-        self._reserve(totals, bytes_seen)
-        v, b, l = planes
-        metas = []
-        for i, bufs in enumerate(self.bufs):
-            metas.append({
-                "kind": self.kinds[i], "is_seq": 1 if self.seqs[i] else 0,
-                **{name: t.data_ptr() for name, t in bufs.items()},
-                "val_base": v[i].data_ptr(),
-                "byte_base": b[i].data_ptr(),
-                "list_base": l[i].data_ptr() if self.seqs[i] else 0,
-            })
-        _native.gpu_extract_fields(data.data_ptr(), r1 - r0, len(self.bufs),
-                                   stats.data_ptr(), metas,
-                                   meta_dev.data_ptr(), err.data_ptr(),
-                                   _stream(), avg_bytes, r0=r0)
+    def confirm(self, totals):
+        """Every row up to the running totals `totals` has been extracted."""
         self.filled = [[int(totals[d][i]) for i in range(len(self.bufs))]
                        for d in range(3)]
 
-    def columns(self, stats, val_base, list_base, R: int) -> List[WireColumn]:
-        """Wire columns of rows [0, R), all extracted. stats is [R,F,6];
-        row f of a plane cut to [:R + 1] is field f's row_off / list_off."""
+    def extract(self, data, stats, planes, presence, r0: int, r1: int,
+                meta: _MetaTable, err, avg_bytes: int, gate=None):
+        """Launch the extraction of records [r0, r1) into the buffers as
+        they are. stats is the FieldStat tensor from row 0, planes the three
+        [F][stride] prefix-sum planes, presence the u8 [F][stride] plane.
+        gate = (broken, crc, scan error, verdict) word addresses: the launch
+        then checks on the device that the scan was clean and that the
+        totals after row r1 fit, and writes nothing otherwise."""
+        v, b, l = planes
+        metas = []
+        for i, bufs in enumerate(self.bufs):
+            vals = bufs["i64_vals" if self.kinds[i] == KIND_INT64 else "f32_vals"]
+            metas.append({
+                "kind": self.kinds[i], "is_seq": 1 if self.seqs[i] else 0,
+                **{name: t.data_ptr() for name, t in bufs.items()},
+                "presence": presence[i].data_ptr(),
+                "val_base": v[i].data_ptr(),
+                "byte_base": b[i].data_ptr(),
+                "list_base": l[i].data_ptr() if self.seqs[i] else 0,
+                "cap_vals": vals.numel(),
+                "cap_bytes": bufs["bytes_data"].numel(),
+                "cap_elem_off": bufs["elem_off"].numel(),
+                "cap_sub_off": bufs["sub_off"].numel(),
+            })
+        g_broken, g_crc, g_err, g_out = gate or (0, 0, 0, 0)
+        _native.gpu_extract_fields(data.data_ptr(), r1 - r0, len(self.bufs),
+                                   stats.data_ptr(), metas,
+                                   meta.dev.data_ptr(), err.data_ptr(),
+                                   _stream(), avg_bytes, r0=r0,
+                                   upload=meta.changed(metas),
+                                   gate_broken=g_broken, gate_crc=g_crc,
+                                   gate_err=g_err, gate_out=g_out)
+
+    def columns(self, presence, val_base, list_base, R: int) -> List[WireColumn]:
+        """Wire columns of rows [0, R), all extracted and confirmed: views
+        of what the kernels wrote, no launch. Row f of a plane cut to
+        [:R + 1] is field f's row_off / list_off."""
         cols = []
         for i, bufs in enumerate(self.bufs):
             kind, seq = self.kinds[i], self.seqs[i]
             nv, nb, nl = (self.filled[d][i] for d in range(3))
-            presence = (stats[:, i, 0] >= 0).to(torch.uint8)
-            elem_off = None
-            if kind == KIND_BYTES:
-                elem_off = excl_sum(bufs["elem_len"][:nv])
-            sub_off = None
-            if seq:
-                sub_off = excl_sum(bufs["sub_count"][:nl])
             values = (bufs["i64_vals"][:nv] if kind == KIND_INT64 else
                       bufs["f32_vals"][:nv] if kind == KIND_FLOAT else
                       bufs["bytes_data"][:nb])
-            cols.append(WireColumn(kind, seq, presence, val_base[i][:R + 1],
-                                   values, elem_off,
-                                   list_base[i][:R + 1] if seq else None,
-                                   sub_off))
+            cols.append(WireColumn(
+                kind, seq, presence[i][:R], val_base[i][:R + 1], values,
+                bufs["elem_off"][:nv + 1] if kind == KIND_BYTES else None,
+                list_base[i][:R + 1] if seq else None,
+                bufs["sub_off"][:nl + 1] if seq else None))
         return cols
 
 
@@ -758,19 +794,21 @@ def write_batch_to_file(batch: RecordBatch, path: str,
 
 # what the last read_file_to_batch_pipelined call on a registered mapping did:
 # path = "streamed" | "fallback" (streamed attempt abandoned) | "unstreamed"
-# (TFREC_STREAM_DECODE=0), the slice count and the row-buffer regrows
+# (TFREC_STREAM_DECODE=0), the slice count, the buffer regrows and how often
+# the streamed path blocked on the device (host_waits)
 last_read = {}
 
 # words of the streamed read's status block
-_ST_BROKEN, _ST_CRC, _ST_ERR, _ST_XERR, _ST_CARRY = 0, 1, 2, 3, 4
+_ST_BROKEN, _ST_CRC, _ST_ERR, _ST_XERR, _ST_NOEXT, _ST_CARRY = 0, 1, 2, 3, 4, 5
 
 
 class _StreamStatus:
-    """One int64 status block per streamed read, read back whole: the
-    broken-chain flag, the fused CRC word (all-ones = clean), the scan's
-    int32 codec error pair, the extraction's, then one word per chain
-    launch: word k is the end of the k-th launch's last candidate and the
-    carry into the next (the carry into the first is 0)."""
+    """One int64 status block per streamed read: the broken-chain flag, the
+    fused CRC word (all-ones = clean), the scan's int32 codec error pair, the
+    extraction's, the extraction gate's verdict (1 = the last gated launch
+    wrote nothing), then one word per chain launch: word k is the end of the
+    k-th launch's last candidate and the carry into the next (the carry into
+    the first is 0)."""
 
     def __init__(self, max_chains: int, device):
         self.words = torch.zeros(_ST_CARRY + 1 + max_chains, dtype=torch.int64,
@@ -786,29 +824,33 @@ class _StreamStatus:
         """Carry into chain launch k == end of launch k - 1."""
         return self.addr(_ST_CARRY + k)
 
-    def head(self) -> torch.Tensor:
-        """The words before the carries: all that scan_error() reads."""
-        return self.words[:_ST_CARRY]
 
-    # decoding a host copy of the block (or of its head)
-    @staticmethod
-    def chain_end(h, nchain: int) -> Optional[int]:
-        """End of the chain after nchain launches; None once it broke."""
-        return None if int(h[_ST_BROKEN]) != 0 else int(h[_ST_CARRY + nchain])
+class _Snapshot:
+    """Host copy of one gpu_stream_snapshot block: the slice's candidate
+    count, the status head words, the chain end so far and the running
+    totals [3][F] at the row the snapshot was taken for."""
 
-    @staticmethod
-    def scan_error(h):
-        """(crc word, codec rc, 1 + offending record) of the rows scanned."""
-        pair = h[_ST_ERR:_ST_ERR + 1].view(torch.int32)
-        return int(h[_ST_CRC]), int(pair[0]), int(pair[1])
+    def __init__(self, h: np.ndarray, F: int):
+        self.count = int(h[0])
+        st = h[1:1 + _ST_CARRY]
+        self.broken = int(st[_ST_BROKEN]) != 0
+        pair = st[_ST_ERR:_ST_ERR + 1].view(np.int32)
+        # (crc word, codec rc, 1 + offending record) of the rows scanned
+        self.scan_error = (int(st[_ST_CRC]), int(pair[0]), int(pair[1]))
+        xpair = st[_ST_XERR:_ST_XERR + 1].view(np.int32)
+        self.xerr = (int(xpair[0]), int(xpair[1]))
+        self.refused = int(st[_ST_NOEXT]) != 0
+        self.chain_end = int(h[1 + _ST_CARRY])
+        self.totals = h[2 + _ST_CARRY:].reshape(3, F) if F else None
 
 
 class _StreamRows:
     """Row-indexed buffers of one streamed read: candidate pos/len, payload
-    off and (F > 0) the FieldStat rows. Sized from the record density of the
-    first slice that yields candidates times _STREAM_HEADROOM; reserve() is
-    called on the host before every launch that writes rows, and regrows by
-    copying the filled rows when the launch would not fit."""
+    off and (F > 0) the FieldStat rows, the prefix-sum planes and the
+    presence plane. Sized from the record density of the first slice that
+    yields candidates times _STREAM_HEADROOM; reserve() is called on the
+    host before every launch that writes rows, and regrows by copying the
+    filled rows when the launch would not fit."""
 
     def __init__(self, total_bytes: int, F: int, device):
         self.total_bytes = total_bytes
@@ -819,18 +861,22 @@ class _StreamRows:
         # exclusive prefix sums of nvals/nbytes/nlists, [F][cap + 1] each;
         # row f cut to [:R + 1] is the contiguous row_off of field f
         self.planes = None
+        # u8 [F][cap], written by the extraction
+        self.presence = None
 
     def _alloc(self, cap: int):
         i64 = dict(dtype=torch.int64, device=self.device)
-        planes = None
+        planes = presence = None
         if self.F:
             planes = [torch.empty((self.F, cap + 1), **i64) for _ in range(3)]
             for t in planes:
                 t[:, 0] = 0
+            presence = torch.empty((self.F, cap), dtype=torch.uint8,
+                                   device=self.device)
         return (torch.empty(cap, **i64), torch.empty(cap, **i64),
                 torch.empty(cap, **i64),
                 torch.empty((cap, self.F, 6), **i64) if self.F else None,
-                planes)
+                planes, presence)
 
     def cand_ptrs(self, c: int):
         """Addresses of candidate c's (pos, len, off) entries."""
@@ -852,18 +898,14 @@ class _StreamRows:
                                b.data_ptr(), l.data_ptr(), _stream(), r0=r0,
                                r1=r1, stride=self.cap + 1)
 
-    def totals(self, r: int) -> list:
-        """Running totals after r rows: three [F] device views."""
-        return [t[:, r] for t in self.planes]
-
     def reserve(self, need: int, n_cand: int, n_scanned: int, bytes_seen: int):
         """Make room for `need` rows; rows [0, n_cand) of pos/len/off and
-        [0, n_scanned) of stats are live."""
+        [0, n_scanned) of stats, planes and presence are live."""
         cap = stream_plan.grown_capacity(self.cap, need, bytes_seen,
                                          self.total_bytes, _STREAM_HEADROOM)
         if cap == self.cap:
             return
-        pos, lens, off, stats, planes = self._alloc(cap)
+        pos, lens, off, stats, planes, presence = self._alloc(cap)
         if n_cand:
             pos[:n_cand].copy_(self.pos[:n_cand])
             lens[:n_cand].copy_(self.lens[:n_cand])
@@ -872,8 +914,9 @@ class _StreamRows:
             stats[:n_scanned].copy_(self.stats[:n_scanned])
             for new, old in zip(planes, self.planes):
                 new[:, :n_scanned + 1].copy_(old[:, :n_scanned + 1])
+            presence[:, :n_scanned].copy_(self.presence[:, :n_scanned])
         self.pos, self.lens, self.off, self.stats = pos, lens, off, stats
-        self.planes = planes
+        self.planes, self.presence = planes, presence
         if self.cap:
             last_read["regrows"] = last_read.get("regrows", 0) + 1
         self.cap = cap
@@ -881,9 +924,13 @@ class _StreamRows:
 
 class _StreamedRead:
     """State and steps of one streamed read over `data`, whose slices are
-    still landing. Per slice, in order: discover() its candidates, arrived()
-    decides how many records lie inside the bytes that have landed, scan()
-    decodes them; finish() runs after the last slice."""
+    still landing. step() runs once per landed slice and blocks on the device
+    once: a snapshot that brings the slice's candidate count together with
+    what became of the previous slice's launches. Everything it then
+    launches (EMIT, chain, structure scan, stat scan, extraction) decides on
+    the device whether it may run: the scan looks at the broken-chain word,
+    the extraction at extract_gate_kernel's verdict. finish() runs after the
+    last slice."""
 
     def __init__(self, data: torch.Tensor, nslices: int, schema: StructType,
                  record_type: str, verify_crc: bool):
@@ -902,115 +949,165 @@ class _StreamedRead:
         if self.do_scan:
             self.blob = _schema_blob_device(schema, device)
             self.vals = _FieldValues(fields, self.n, device)
-            self.meta_dev = torch.empty(F * _native.gpu_devmeta_bytes(),
-                                        dtype=torch.uint8, device=device)
+            self.meta = _MetaTable(F, device)
         self.C = 0       # chained candidates so far
         self.nchain = 0  # chain launches so far
-        self.r_done = 0  # records structure-scanned so far
-        self.x_done = 0  # records extracted so far
+        self.r_done = 0  # records whose structure scan has been launched
+        self.x_done = 0  # records whose extraction is confirmed
+        self.x_pending = None  # end row of a gated extraction not yet confirmed
+        self.sized = False  # value buffers sized from a measured density
+        self.bytes_done = 0  # bytes the scanned rows lie in
         self.clean = True  # False once a scanned range reported an error
         self.avg_bytes = None
 
-    def discover(self, p: stream_plan.SlicePlan, counts: torch.Tensor):
-        """Step 1: prefix-sum the slice's per-block candidate counts, make
-        room, EMIT the candidates behind the earlier ones and chain them on
-        from the previous launch's end."""
-        # host syncs cost nothing while later slices are in flight
-        block_off = excl_sum(counts)
-        c_s = int(block_off[-1].item())
-        if not c_s:
-            return
-        self.rows.reserve(self.C + c_s, self.C, self.r_done, p.scan_hi)
-        pos, lens, off = self.rows.cand_ptrs(self.C)
-        _native.gpu_frame_scan_emit(self.data.data_ptr(), self.n, p.scan_lo,
-                                    p.scan_hi, 0, block_off.data_ptr(), pos,
-                                    lens, _stream())
-        _native.gpu_frame_chain(pos, lens, c_s,
-                                self.status.carry_addr(self.nchain),
-                                self.status.carry_addr(self.nchain + 1), off,
-                                self.status.addr(_ST_BROKEN), _stream())
-        self.nchain += 1
-        self.C += c_s
+    def _snapshot(self, count_ptr: int, r: int) -> _Snapshot:
+        """Block until everything launched so far has run; bring back the
+        status words, the chain end, the running totals at row r and the
+        word at count_ptr."""
+        F = self.F if self.rows.planes is not None else 0
+        n = 2 + _ST_CARRY + 3 * F
+        buf = pinned_buffer("snapshot", n * 8)
+        v, b, l = ([t.data_ptr() for t in self.rows.planes] if F
+                   else (0, 0, 0))
+        _native.gpu_stream_snapshot(
+            count_ptr, self.status.addr(0), _ST_CARRY,
+            self.status.carry_addr(self.nchain), v, b, l, self.rows.cap + 1,
+            F, r, buf.data_ptr(), _stream())
+        _native.gpu_stream_snapshot_wait()
+        last_read["host_waits"] = last_read.get("host_waits", 0) + 1
+        return _Snapshot(buf.numpy()[:n * 8].view(np.int64).copy(), F)
 
-    def arrived(self, p: stream_plan.SlicePlan, last: bool):
-        """Step 2: (records that have fully arrived, bytes they span) once
-        slice p has landed; None when the chain broke."""
-        if not self.do_scan or self.C == self.r_done:
-            return self.r_done, p.b1
-        if last:
-            # every candidate ends inside the file (the COUNT cull), so all
-            # of them have arrived; the chain flag rides the final readback
-            return self.C, self.n
-        end = self.status.chain_end(self.status.words.cpu(), self.nchain)
-        if end is None:
-            return None
-        avail = stream_plan.arrived_records(self.C, end, p.b1)
-        return avail, end if avail == self.C else p.b1
-
-    def scan(self, avail: int, end: int, last: bool):
-        """Step 3: structure-scan (+CRC) records [r_done, avail), extend the
-        stat prefix sums over them and, under the later slices' DMA, extract
-        their values. The last slice's rows wait for finish()."""
-        r0 = self.r_done
-        if avail <= r0:
-            return
-        if self.avg_bytes is None:  # wave/lane choice: once per file
-            self.avg_bytes = max(0, end // avail - 16)
-        off, lens, stats = self.rows.row_ptrs(r0)
-        _native.gpu_scan_records(
-            self.data.data_ptr(), off, lens, avail - r0, FMT[self.record_type],
-            self.blob.data_ptr(), self.F, stats, self.status.err.data_ptr(),
-            self.status.addr(_ST_CRC) if self.verify_crc else 0, _stream(),
-            self.avg_bytes, rec_base=r0)
-        self.rows.scan_stats(r0, avail)
-        self.r_done = avail
-        if not _STREAM_EXTRACT or last or not self.clean:
-            return
-        # running totals + error words of the rows scanned so far:
-        # extraction only ever sees rows that scanned clean
-        F = self.F
-        h = torch.cat(self.rows.totals(avail) + [self.status.head()]).cpu()
-        crc_bad, rc, _ = self.status.scan_error(h[3 * F:])
+    def _settle(self, snap: _Snapshot):
+        """What a snapshot at row r_done says about the launches before it:
+        error words stop the extraction (they are raised at the end); a
+        confirmed extraction advances x_done; one the gate refused had totals
+        beyond the buffers, which are now known: regrow."""
+        crc_bad, rc, _ = snap.scan_error
         if crc_bad != -1 or rc != 0:
-            self.clean = False  # keep scanning; raised at the end
+            self.clean = False
+        if self.x_pending is None:
             return
-        self._extract(avail, h[:3 * F].view(3, F), end)
+        assert self.x_pending == self.r_done
+        if not snap.refused:
+            self.x_done = self.x_pending
+            self.vals.confirm(snap.totals)
+        elif self.clean:
+            self.vals.reserve(snap.totals, self.bytes_done)
+        self.x_pending = None
 
-    def _extract(self, r1: int, totals_h, bytes_seen: int):
+    def _extract(self, r1: int, gated: bool):
+        st = self.status
+        gate = (st.addr(_ST_BROKEN), st.addr(_ST_CRC), st.addr(_ST_ERR),
+                st.addr(_ST_NOEXT)) if gated else None
         self.vals.extract(self.data, self.rows.stats, self.rows.planes,
-                          self.x_done, r1, totals_h, bytes_seen, self.meta_dev,
-                          self.status.xerr, self.avg_bytes)
-        self.x_done = r1
+                          self.rows.presence, self.x_done, r1, self.meta,
+                          st.xerr, self.avg_bytes, gate)
+
+    def step(self, p: stream_plan.SlicePlan, counts: Optional[torch.Tensor],
+             last: bool) -> bool:
+        """Slice p has landed and `counts` holds its per-block candidate
+        counts (None: nothing to scan). False when the chain broke."""
+        count_ptr = 0
+        if counts is not None:
+            block_off = excl_sum(counts)
+            count_ptr = block_off.data_ptr() + counts.numel() * 8
+        # the one blocking wait of the slice; later slices are in flight
+        snap = self._snapshot(count_ptr, self.r_done)
+        if snap.broken:
+            return False
+        if self.do_scan:
+            self._settle(snap)
+        c_s = snap.count
+        if c_s:
+            # discovery: make room, EMIT the candidates behind the earlier
+            # ones and chain them on from the previous launch's end
+            self.rows.reserve(self.C + c_s, self.C, self.r_done, p.scan_hi)
+            pos, lens, off = self.rows.cand_ptrs(self.C)
+            _native.gpu_frame_scan_emit(self.data.data_ptr(), self.n,
+                                        p.scan_lo, p.scan_hi, 0,
+                                        block_off.data_ptr(), pos, lens,
+                                        _stream())
+            _native.gpu_frame_chain(pos, lens, c_s,
+                                    self.status.carry_addr(self.nchain),
+                                    self.status.carry_addr(self.nchain + 1),
+                                    off, self.status.addr(_ST_BROKEN),
+                                    _stream())
+            self.nchain += 1
+            self.C += c_s
+        if not self.do_scan:
+            return True
+        # Before the last slice the last chained candidate always waits: in
+        # an unbroken chain every other one ends where its successor starts,
+        # below scan_hi, so it has arrived. After the last slice every
+        # candidate has (they end inside the file: the COUNT cull).
+        avail = stream_plan.launchable_records(self.C, last)
+        r0 = self.r_done
+        if avail > r0:
+            if self.avg_bytes is None:  # wave/lane choice: once per file
+                self.avg_bytes = max(0, p.scan_hi // avail - 16)
+            off, lens, stats = self.rows.row_ptrs(r0)
+            _native.gpu_scan_records(
+                self.data.data_ptr(), off, lens, avail - r0,
+                FMT[self.record_type], self.blob.data_ptr(), self.F, stats,
+                self.status.err.data_ptr(),
+                self.status.addr(_ST_CRC) if self.verify_crc else 0, _stream(),
+                self.avg_bytes, rec_base=r0,
+                gate=self.status.addr(_ST_BROKEN))
+            self.rows.scan_stats(r0, avail)
+            self.r_done = avail
+        self.bytes_done = p.scan_hi
+        if not _STREAM_EXTRACT or not self.clean or avail <= self.x_done:
+            return True
+        if not self.sized:
+            if last:
+                return True  # finish() sizes exactly
+            # The first extraction sizes every value buffer from measured
+            # density: one more wait, under the later slices' copies. From
+            # here on extraction is optimistic and the gate catches a jump.
+            snap = self._snapshot(0, avail)
+            if snap.broken:
+                return False
+            self._settle(snap)
+            if not self.clean:
+                return True
+            self.vals.reserve(snap.totals, p.scan_hi)
+            self.sized = True
+        self._extract(avail, gated=True)
+        self.x_pending = avail
+        return True
 
     def finish(self) -> Optional[RecordBatch]:
-        """Step 4, after the last slice: one packed readback, the errors in
+        """After the last slice: the final snapshot, the errors in
         decode_device's order, the rows not yet extracted, the columns. None
         when the chain did not hold over the whole file."""
-        R, F, n = self.C, self.F, self.n
+        R, n = self.C, self.n
         if R == 0:
             return None
+        snap = self._snapshot(0, R)
+        if snap.broken or snap.chain_end != n:
+            return None
         if not self.do_scan:
-            if self.status.chain_end(self.status.words.cpu(), self.nchain) != n:
-                return None
             return decode_device(self.data, self.rows.off[:R],
                                  self.rows.lens[:R], self.schema,
                                  self.record_type, self.verify_crc)
-        # ONE packed readback: totals, then the status block
-        packed = torch.cat(self.rows.totals(R) + [self.status.words]).cpu()
-        st_h = packed[3 * F:]
-        if self.status.chain_end(st_h, self.nchain) != n:
-            return None
-        crc_bad, rc, rec1 = self.status.scan_error(st_h)
+        crc_bad, rc, rec1 = snap.scan_error
         _raise_scan_errors(crc_bad if self.verify_crc else -1, rc, rec1)
         if not self.clean:
             raise RuntimeError("streamed decode: scan error lost")
+        self._settle(snap)
+        xerr = snap.xerr
         if self.x_done < R:
-            self._extract(R, packed[:3 * F].view(3, F), n)
+            # not streamed, or the gate refused the last launch: every total
+            # is known now, so size exactly and extract (the rare path)
+            self.vals.reserve(snap.totals, n)
+            self._extract(R, gated=False)
+            self.x_done = R
+            self.vals.confirm(snap.totals)
+            xerr = self._snapshot(0, R).xerr
         val_base, _, list_base = self.rows.planes
-        cols = self.vals.columns(self.rows.stats[:R], val_base, list_base, R)
-        err_h = self.status.xerr.cpu()
-        if int(err_h[0]) != 0:
-            _raise_extract_error(int(err_h[0]), int(err_h[1]))
+        cols = self.vals.columns(self.rows.presence, val_base, list_base, R)
+        if xerr[0] != 0:
+            _raise_extract_error(*xerr)
         return RecordBatch(self.schema, cols, R)
 
 
@@ -1087,7 +1184,8 @@ def read_file_to_batch_pipelined(path: str, schema: StructType, record_type: str
     """File -> device batch with the H2D DMA sliced so the work on slice k
     runs while slice k+1 is still in flight: frame discovery (COUNT, prefix
     sum, EMIT), the chain check, the fused structure scan + CRC, the stat
-    prefix sums and the extraction of the records that have fully arrived.
+    prefix sums and the extraction of the records that have fully arrived,
+    with one blocking snapshot per slice (_StreamedRead.step).
     Positions within 32 bytes of a slice boundary are deferred to the next
     slice's launch (their load window extends past the boundary). After the
     last slice only that slice's work remains. A broken frame chain abandons
@@ -1112,7 +1210,7 @@ def read_file_to_batch_pipelined(path: str, schema: StructType, record_type: str
     block_counts = torch.empty(max(sum(_scan_blocks(p) for p in plan), 1),
                                dtype=torch.int64, device=data.device)
     events = _issue_h2d_slices(data, ptr, plan)
-    last_read.update(path="streamed", slices=S, regrows=0)
+    last_read.update(path="streamed", slices=S, regrows=0, host_waits=0)
     unstreamed = (data, plan, block_counts, events)
     decode = (schema, record_type, verify_crc)
     if not _STREAM_DECODE:
@@ -1122,13 +1220,10 @@ def read_file_to_batch_pipelined(path: str, schema: StructType, record_type: str
     base = 0  # block_counts offset of the current slice
     for s, p in enumerate(plan):
         nb = _count_slice(data, p, events[s], block_counts, base)
-        if nb:
-            rd.discover(p, block_counts[base:base + nb])
-            base += nb
-        got = rd.arrived(p, last=s == S - 1)
-        if got is None:
+        counts = block_counts[base:base + nb] if nb else None
+        base += nb
+        if not rd.step(p, counts, last=s == S - 1):
             return _read_unstreamed(*unstreamed, s + 1, *decode)
-        rd.scan(*got, last=s == S - 1)
     batch = rd.finish()
     if batch is None:
         return _read_unstreamed(*unstreamed, S, *decode)

@@ -51,6 +51,17 @@ def arrived_records(n_cand: int, last_end: int, arrived: int) -> int:
     return n_cand if last_end <= arrived else n_cand - 1
 
 
+def launchable_records(n_cand: int, last: bool) -> int:
+    """Of n_cand chained candidates, how many a slice's launches may cover
+    without the host reading the chain end first. Before the last slice the
+    last candidate always waits for the next slice (one record of deferral
+    per slice): every other one ends where its successor starts, i.e. below
+    the scanned range's end. After the last slice all of them have arrived."""
+    if n_cand <= 0:
+        return 0
+    return n_cand if last else n_cand - 1
+
+
 def row_capacity(need: int, bytes_seen: int, total_bytes: int,
                  headroom: float, min_unit: int = MIN_FRAME) -> int:
     """Capacity, in rows, for a file of total_bytes of which bytes_seen held
