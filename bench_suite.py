@@ -12,6 +12,9 @@ driver runs it). This suite covers the rest, each printing one JSON line:
   infer           config 4: SequenceExample (FeatureList of FloatList)
                   schema inference; with WORLD_SIZE>1 the per-feature
                   lattice codes are max-all-reduced over RCCL
+  gzip_write      GPU-engine gzip write, host zlib vs the device compressor
+                  (gzip_engine="host" | "device"), on flagship-shaped
+                  Example rows and on config 5's random ByteArray payloads
   gzip_bytearray  config 5: gzip-compressed ByteArray read, shard staged
                   through HBM on the GPU engine
 
@@ -265,8 +268,76 @@ def bench_gzip_bytearray(args):
           world if use_cuda else 0)
 
 
+def _flagship_table(rows, seed):
+    """bench.py's Example shape as an Arrow table: int64 id, Int64List[8],
+    FloatList[16], BytesList[2] of ~12-byte tokens (~220 B/record)."""
+    import pyarrow as pa
+
+    rng = np.random.default_rng(seed)
+
+    def lists(values, k):
+        return pa.ListArray.from_arrays(
+            pa.array(np.arange(0, (rows + 1) * k, k, dtype=np.int32)), values)
+
+    toks = [f"tok{i % 997:06d}-{i % 89:02d}" for i in range(2 * rows)]
+    return pa.table({
+        "id": pa.array(rng.integers(0, 2**62, rows).astype(np.int64)),
+        "ints": lists(pa.array(
+            rng.integers(0, 2**31, 8 * rows).astype(np.int64)), 8),
+        "floats": lists(pa.array(rng.random(16 * rows).astype(np.float32)), 16),
+        "tokens": lists(pa.array(toks, type=pa.string()), 2),
+    })
+
+
+def bench_gzip_write(args):
+    """GPU-engine gzip write: host zlib (the default) against the device
+    DEFLATE compressor, same build, same data. Two datasets: Example rows
+    (feature names repeat every record: match-heavy) and config 5's random
+    200-byte ByteArray payloads (incompressible: the stored path)."""
+    import pyarrow as pa
+    import torch
+
+    import spark_tfrecord_amd as stf
+
+    rank, world = _env_world()
+    if not torch.cuda.is_available():
+        raise SystemExit("gzip_write needs the GPU engine")
+    rows = args.rows // max(world, 1)
+    rng = np.random.default_rng(9 + rank)
+    datasets = [
+        ("example", "Example", _flagship_table(rows, 1 + rank)),
+        ("bytearray", "ByteArray", pa.table({"byteArray": pa.array(
+            [rng.bytes(200) for _ in range(rows)], type=pa.large_binary())})),
+    ]
+    d = _workdir("gzw", rank)
+    for name, rtype, table in datasets:
+        for gz in ("host", "device"):
+            out = os.path.join(d, f"{name}_{gz}")
+
+            def write():
+                stf.write_tfrecord(table, out, record_type=rtype, codec="gzip",
+                                   mode="overwrite", engine="gpu",
+                                   gzip_engine=gz)
+                torch.cuda.synchronize()
+
+            write()  # warm-up: allocator pools, pinned buffers, page cache
+            t0 = time.perf_counter()
+            for _ in range(args.reps):
+                write()
+            el = time.perf_counter() - t0
+            nbytes = sum(os.path.getsize(os.path.join(out, f))
+                         for f in os.listdir(out) if not f.startswith("_"))
+            _emit(rank, f"rows/sec gzip write {name} gzip_engine={gz}",
+                  rows * args.reps / el, "rows/s",
+                  {"rows": rows, "dataset": name, "gzip_engine": gz,
+                   "gz_bytes": nbytes, "engine": "gpu", "reps": args.reps},
+                  el, 1)
+    shutil.rmtree(d, ignore_errors=True)
+
+
 BENCHES = {"plumbing": bench_plumbing, "partitionby": bench_partitionby,
-           "infer": bench_infer, "gzip_bytearray": bench_gzip_bytearray}
+           "infer": bench_infer, "gzip_bytearray": bench_gzip_bytearray,
+           "gzip_write": bench_gzip_write}
 
 
 def main():

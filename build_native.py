@@ -16,7 +16,8 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parent
 OUT = ROOT / "spark_tfrecord_amd" / "_native.so"
 SOURCES = [ROOT / "csrc" / "ext.cpp", ROOT / "csrc" / "hip" / "kernels.hip",
-           ROOT / "csrc" / "hip" / "inflate.hip"]
+           ROOT / "csrc" / "hip" / "inflate.hip",
+           ROOT / "csrc" / "hip" / "deflate.hip"]
 HEADERS = list((ROOT / "csrc").rglob("*.h"))
 
 

@@ -236,6 +236,85 @@ TFR_HOSTDEV inline uint32_t crc32c_combine_fast(uint32_t crc1, uint32_t crc2,
   return crc_gfmul(crc1, crc32c_shift_elem(len2)) ^ crc2;
 }
 
+// ---------------------------------------------------------------------------
+// CRC-32 (IEEE 802.3, reflected 0xEDB88320): the gzip trailer's checksum,
+// computed by the device DEFLATE compressor (csrc/hip/deflate.hip). Same
+// slicing-by-8 walker (crc32c_sw takes the tables) and the same field-form
+// shift/combine, over the other polynomial.
+// ---------------------------------------------------------------------------
+
+constexpr uint32_t kCrc32IeeePoly = 0xEDB88320u;
+
+constexpr Crc32cTables make_crc32_ieee_tables() {
+  Crc32cTables tb{};
+  for (uint32_t i = 0; i < 256; ++i) {
+    uint32_t c = i;
+    for (int k = 0; k < 8; ++k)
+      c = (c & 1) ? (kCrc32IeeePoly ^ (c >> 1)) : (c >> 1);
+    tb.t[0][i] = c;
+  }
+  for (uint32_t i = 0; i < 256; ++i) {
+    uint32_t c = tb.t[0][i];
+    for (int s = 1; s < 8; ++s) {
+      c = tb.t[0][c & 0xFF] ^ (c >> 8);
+      tb.t[s][i] = c;
+    }
+  }
+  return tb;
+}
+
+inline constexpr Crc32cTables kCrcIeeeTables = make_crc32_ieee_tables();
+
+TFR_HOSTDEV inline uint32_t crc32_ieee(const uint8_t* p, size_t n,
+                                       uint32_t crc = 0) {
+  return crc32c_sw(p, n, crc, kCrcIeeeTables.t);
+}
+
+TFR_HOSTDEV constexpr uint32_t crc_ieee_mulx(uint32_t c) {
+  return (c >> 1) ^ (kCrc32IeeePoly & (0u - (c & 1u)));
+}
+
+TFR_HOSTDEV constexpr uint32_t crc_ieee_gfmul(uint32_t a, uint32_t b) {
+  uint32_t res = 0;
+  uint32_t cur = a;
+  for (int i = 31; i >= 0; --i) {
+    if ((b >> i) & 1u) res ^= cur;
+    cur = crc_ieee_mulx(cur);
+  }
+  return res;
+}
+
+constexpr CrcPow2 make_crc_ieee_pow2() {
+  CrcPow2 t{};
+  t.p[0] = crc_ieee_mulx(0x80000000u);
+  for (int k = 1; k < 64; ++k)
+    t.p[k] = crc_ieee_gfmul(t.p[k - 1], t.p[k - 1]);
+  return t;
+}
+
+inline constexpr CrcPow2 kCrcIeeePow2 = make_crc_ieee_pow2();
+
+// alpha^(8*nbytes) for the IEEE polynomial; callers folding many
+// equal-length pieces build it once.
+TFR_HOSTDEV inline uint32_t crc32_ieee_shift_elem(uint64_t nbytes) {
+  uint64_t e = nbytes << 3;
+  uint32_t t = 0x80000000u;
+  int k = 0;
+  while (e) {
+    if (e & 1u) t = crc_ieee_gfmul(t, kCrcIeeePow2.p[k]);
+    e >>= 1;
+    ++k;
+  }
+  return t;
+}
+
+// crc(A||B) from crc(A), crc(B) and len(B) (all finalized CRC-32 values).
+TFR_HOSTDEV inline uint32_t crc32_ieee_combine(uint32_t crc1, uint32_t crc2,
+                                               uint64_t len2) {
+  if (len2 == 0) return crc1;
+  return crc_ieee_gfmul(crc1, crc32_ieee_shift_elem(len2)) ^ crc2;
+}
+
 TFR_HOSTDEV inline uint32_t unmask_crc(uint32_t masked) {
   uint32_t rot = masked - kMaskDelta;
   return (rot << 15) | (rot >> 17);

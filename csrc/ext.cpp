@@ -21,6 +21,7 @@
 #include <cstring>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <stdexcept>
 #include <string>
@@ -28,6 +29,7 @@
 #include <vector>
 
 #include "codec_core.h"
+#include "deflate_core.h"
 #include "inflate_core.h"
 
 namespace py = pybind11;
@@ -761,6 +763,48 @@ py::bytes host_inflate_segment(py::buffer comp, i64 expect) {
   return py::bytes(out);
 }
 
+// Host runs of the DEFLATE segment compressor core shared with the gfx950
+// kernel (csrc/deflate_core.h): `lane` < 0 emulates the lanes with loops and
+// is byte-identical to the device, which backs the CPU tests.
+py::bytes host_deflate_segment(py::buffer data, bool final,
+                               double stored_threshold) {
+  auto info = data.request();
+  i64 n = static_cast<i64>(info.size * info.itemsize);
+  i64 cap = tfrec::deflate::seg_out_bound(n);
+  std::string out(static_cast<size_t>(cap), '\0');
+  std::vector<u32> toks(static_cast<size_t>(n > 0 ? n : 1), 0xA5A5A5A5u);
+  // LDS starts out with whatever the last block left there: the host run
+  // must not lean on zeroed scratch either
+  std::unique_ptr<tfrec::deflate::Scratch> S(new tfrec::deflate::Scratch);
+  std::memset(static_cast<void*>(S.get()), 0xA5,
+              sizeof(tfrec::deflate::Scratch));
+  i64 len = tfrec::deflate::deflate_one(
+      static_cast<const u8*>(info.ptr), n, reinterpret_cast<u8*>(&out[0]), cap,
+      final, stored_threshold, toks.data(), *S);
+  if (len < 0) throw std::runtime_error("deflate_one failed");
+  return py::bytes(out.data(), static_cast<size_t>(len));
+}
+
+std::vector<int> host_huffman_lengths(const std::vector<u32>& freqs,
+                                      int max_len) {
+  if (freqs.size() > 288 || max_len < 1 || max_len > 15)
+    throw std::invalid_argument(
+        "host_huffman_lengths: <= 288 symbols, max_len in 1..15");
+  std::vector<u8> len(freqs.size() + 1, 0);
+  std::unique_ptr<tfrec::deflate::HuffWs> W(new tfrec::deflate::HuffWs);
+  std::memset(static_cast<void*>(W.get()), 0xA5,
+              sizeof(tfrec::deflate::HuffWs));
+  tfrec::deflate::build_lengths(freqs.data(), static_cast<int>(freqs.size()),
+                                max_len, len.data(), *W, -1);
+  return std::vector<int>(len.begin(), len.begin() + freqs.size());
+}
+
+u32 crc32_ieee_py(py::buffer data) {
+  auto info = data.request();
+  return crc32_ieee(static_cast<const u8*>(info.ptr),
+                    static_cast<size_t>(info.size * info.itemsize));
+}
+
 u32 crc32c_py(py::buffer data) {
   py::buffer_info info;
   BufView buf = as_bytes(data, info);
@@ -777,6 +821,7 @@ u32 masked_crc32c_py(py::buffer data) {
 
 void register_gpu(py::module_& m);      // defined in csrc/hip/kernels.hip
 void register_inflate(py::module_& m);  // defined in csrc/hip/inflate.hip
+void register_deflate(py::module_& m);  // defined in csrc/hip/deflate.hip
 
 PYBIND11_MODULE(_native, m) {
   m.doc() = "MI355X-native TFRecord codec (host + gfx950 kernels)";
@@ -798,6 +843,13 @@ PYBIND11_MODULE(_native, m) {
   m.def("host_inflate_segment", &host_inflate_segment, py::arg("comp"),
         py::arg("expect"),
         "TEST-ONLY: run the device inflater's core on host for one segment");
+  m.def("host_deflate_segment", &host_deflate_segment, py::arg("data"),
+        py::arg("final"), py::arg("stored_threshold"),
+        "TEST-ONLY: run the device compressor's core on host for one segment");
+  m.def("host_huffman_lengths", &host_huffman_lengths, py::arg("freqs"),
+        py::arg("max_len"),
+        "TEST-ONLY: length-limited Huffman code lengths of the compressor core");
+  m.def("crc32_ieee", &crc32_ieee_py, "CRC-32 (IEEE, gzip) of a byte buffer");
   m.def("crc32c_combine_fast",
         [](u32 c1, u32 c2, u64 len2) { return crc32c_combine_fast(c1, c2, len2); },
         "crc(A||B) via register-only GF(2^32) field multiply (wave-CRC form)");
@@ -822,6 +874,7 @@ PYBIND11_MODULE(_native, m) {
 #ifdef TFREC_WITH_HIP
   register_gpu(m);
   register_inflate(m);
+  register_deflate(m);
   m.attr("HAS_GPU_KERNELS") = true;
 #else
   m.attr("HAS_GPU_KERNELS") = false;

@@ -151,6 +151,7 @@ class DataFrameWriter(_OptionsMixin):
             schema=self._df.schema,
             num_shards=int(self._options.get("num_shards", 1)),
             engine=self._options.get("engine", "auto"),
+            gzip_engine=self._options.get("gzipengine"),
         )
 
 

@@ -1332,6 +1332,67 @@ def read_gzip_file_to_device(path: str, device="cuda") -> Optional[torch.Tensor]
     return data
 
 
+def _deflate_max_waves(device) -> int:
+    """Resident-wave cap of the compressor launch: its token workspace is
+    sized per resident wave (4 B per input byte of one segment), not per
+    segment. 78 KiB of LDS per 4-wave block fits two blocks per CU."""
+    return 8 * torch.cuda.get_device_properties(device).multi_processor_count
+
+
+def gzip_image_device(img: torch.Tensor, seg: Optional[int] = None) -> torch.Tensor:
+    """Uncompressed file image in HBM -> complete gzip file image in HBM, in
+    the layout io/paths.py compress_bytes writes (FEXTRA 'TS' segment
+    table, independent full-flush segments, CRC-32/ISIZE trailer), via the
+    device compressor (csrc/hip/deflate.hip). The layout is known up front,
+    so the only host round trip is one read of the final image size."""
+    from ..io import paths as P
+
+    check_native()
+    if img.dtype != torch.uint8 or img.dim() != 1 or not img.is_contiguous():
+        raise ValueError("gzip_image_device expects a contiguous 1-D uint8 tensor")
+    n = img.numel()
+    if seg is None:
+        seg = P._gz_segment_size(n)
+    seg = int(seg)
+    if seg <= 0:
+        raise ValueError(f"segment size must be positive, got {seg}")
+    nseg = max(1, -(-n // seg))
+    if nseg > P._GZ_MAX_SEGS:
+        raise ValueError(
+            f"{n} bytes in {seg}-byte segments need {nseg} segments; the "
+            f"gzip segment table holds at most {P._GZ_MAX_SEGS}")
+    device = img.device
+    seg_max = min(seg, n)
+    slot = (_native.deflate_seg_out_bound(seg_max) + 7) & ~7
+    nwaves = min(-(-nseg // 4) * 4, _deflate_max_waves(device))
+    tok_cap = max(seg_max, 1)
+    staging = torch.empty(nseg * slot, dtype=torch.uint8, device=device)
+    tok_ws = torch.empty(nwaves * tok_cap, dtype=torch.int32, device=device)
+    comp_len = torch.empty(nseg, dtype=torch.int64, device=device)
+    comp_off = torch.empty(nseg + 1, dtype=torch.int64, device=device)
+    seg_crc = torch.empty(nseg, dtype=torch.int32, device=device)
+    err = torch.full((1,), -1, dtype=torch.int64, device=device)
+    result = torch.empty(2, dtype=torch.int64, device=device)
+    body_off = 20 + 8 * nseg
+    out_cap = body_off + nseg * slot + 8
+    out = torch.empty(out_cap, dtype=torch.uint8, device=device)
+    _native.gpu_deflate_segments(
+        img.data_ptr(), n, seg, nseg, staging.data_ptr(), slot,
+        comp_len.data_ptr(), seg_crc.data_ptr(), tok_ws.data_ptr(), tok_cap,
+        nwaves, float(P._GZ_STORED_THRESHOLD), err.data_ptr(), _stream())
+    _excl_sum_into(comp_off.data_ptr(), comp_len.data_ptr(), 1, nseg, device)
+    _native.gpu_gzip_assemble(
+        staging.data_ptr(), slot, comp_len.data_ptr(), comp_off.data_ptr(),
+        seg_crc.data_ptr(), n, seg, nseg, out.data_ptr(), out_cap,
+        err.data_ptr(), result.data_ptr(), _stream())
+    size, err_word = (int(v) for v in result.tolist())
+    if err_word != -1:
+        raise RuntimeError(
+            f"device deflate failed: segment {(err_word >> 8) - 1}, "
+            f"cause {err_word & 0xFF}")
+    return out[:size]
+
+
 def read_files_to_batch(paths, schema: StructType, record_type: str,
                         verify_crc: bool = True, device="cuda"):
     """Decode MANY files as ONE GPU pipeline: their (decompressed) images

@@ -208,10 +208,48 @@ def _single_shard_pipelined(table: pa.Table, schema: StructType,
         metrics.add(rows=R, nbytes=nbytes, files=1)
 
 
+GZIP_ENGINES = ("host", "device")
+
+
+def _resolve_gzip_engine(gzip_engine: Optional[str], eng: str,
+                         codec: Optional[str]) -> bool:
+    """True when gzip output is compressed in HBM (csrc/hip/deflate.hip)
+    instead of by host zlib. None = the default: "host", or what
+    TFREC_GZ_ENGINE says for GPU-engine writes. Only the gzip codec has a
+    device compressor; for any other codec the choice is ignored."""
+    explicit = gzip_engine is not None
+    if not explicit:
+        gzip_engine = (os.environ.get("TFREC_GZ_ENGINE", "host")
+                       if eng == "gpu" else "host")
+    val = str(gzip_engine).lower()
+    if val not in GZIP_ENGINES:
+        raise ValueError(
+            f"Unsupported gzip engine {gzip_engine!r} (expected one of "
+            f"{GZIP_ENGINES})")
+    if val == "device" and eng != "gpu":
+        raise ValueError(
+            'gzip_engine="device" needs the GPU engine; this write resolved '
+            f"to engine={eng!r}")
+    return val == "device" and codec == "gzip"
+
+
+def _device_image_to_pinned(img, tag: str, gzip_device: bool) -> np.ndarray:
+    """ONE D2H of a device file image into the tag's pinned buffer. With
+    `gzip_device` the image is gzip-compressed in HBM first, so only the
+    compressed bytes cross the host link. Returns the pinned view (valid
+    until the tag's next use)."""
+    from ..engine import gpu as gpu_engine
+
+    if gzip_device:
+        img = gpu_engine.gzip_image_device(img)
+    return gpu_engine.device_to_pinned_view(img, tag=tag)
+
+
 def _encode_and_write(table: pa.Table, schema: StructType, record_type: str,
                       out_dir: str, codec: Optional[str], job_id: str,
                       num_shards: int, shard_offset: int, eng: str,
-                      metrics: Optional[IOMetrics] = None):
+                      metrics: Optional[IOMetrics] = None,
+                      gzip_device: bool = False):
     """Encode `table` into `num_shards` part files under out_dir. The
     compress+write of shard k runs on a worker thread while shard k+1
     encodes (both the native encoder and zlib release the GIL)."""
@@ -221,7 +259,8 @@ def _encode_and_write(table: pa.Table, schema: StructType, record_type: str,
     bounds = np.linspace(0, R, num_shards + 1).astype(np.int64)
 
     def _compress_write(raw: bytes, fpath: str, rows: int):
-        payload = P.compress_bytes(raw, codec)
+        # with gzip_device, `raw` already is the compressed file image
+        payload = raw if gzip_device else P.compress_bytes(raw, codec)
         P.write_file_atomic(payload, fpath)
         if metrics is not None:
             metrics.add(rows=rows, nbytes=len(payload), files=1)
@@ -241,7 +280,7 @@ def _encode_and_write(table: pa.Table, schema: StructType, record_type: str,
 
             img = gpu_engine.encode_device(
                 gpu_engine.batch_to_device(batch), record_type)
-            raw = gpu_engine.device_to_pinned_view(img, tag="encw0")
+            raw = _device_image_to_pinned(img, "encw0", gzip_device)
         else:
             raw = cpu_engine.encode_batch(batch, record_type)
         _compress_write(raw, fpath, R)
@@ -261,7 +300,7 @@ def _encode_and_write(table: pa.Table, schema: StructType, record_type: str,
 
                 img = gpu_engine.encode_device(
                     gpu_engine.batch_to_device(batch), record_type)
-                raw = gpu_engine.device_to_pinned_view(img, tag="encw0")
+                raw = _device_image_to_pinned(img, "encw0", gzip_device)
             else:
                 raw = cpu_engine.encode_batch(batch, record_type)
             _compress_write(raw, os.path.join(
@@ -295,7 +334,7 @@ def _encode_and_write(table: pa.Table, schema: StructType, record_type: str,
             prev = tag_futs.get(tag)
             if prev is not None:
                 prev.result()  # the tag's pinned buffer is being reused
-            raw = gpu_engine.device_to_pinned_view(img, tag=tag)
+            raw = _device_image_to_pinned(img, tag, gzip_device)
         else:
             raw = cpu_engine.encode_batch(batch, record_type)
         f = pool.submit(_compress_write, raw, fpath, hi - lo)
@@ -312,7 +351,8 @@ def write_tfrecord(data, path: str, record_type: str = "Example",
                    schema: Optional[StructType] = None, num_shards: int = 1,
                    engine: str = "auto", write_success: bool = True,
                    shard_offset: int = 0, job_id: Optional[str] = None,
-                   _apply_mode: bool = True) -> None:
+                   _apply_mode: bool = True,
+                   gzip_engine: Optional[str] = None) -> None:
     """Write DataFrame-shaped `data` as TFRecord files under `path`.
 
     Fault tolerance: every part file lands via write-to-temp + atomic
@@ -320,7 +360,13 @@ def write_tfrecord(data, path: str, record_type: str = "Example",
     partial file visible. Pass an explicit `job_id` to make retries
     idempotent: the rerun produces identical part-file names and atomically
     replaces whatever the failed attempt left behind (the analog of Spark's
-    task-commit protocol the reference relies on)."""
+    task-commit protocol the reference relies on).
+
+    `gzip_engine`: "host" (the default; zlib on the host) or "device" (the
+    GPU engine compresses gzip output in HBM and copies only the compressed
+    image to the host). None takes the default, which TFREC_GZ_ENGINE sets
+    for GPU-engine writes. "device" with the CPU engine is an error; with a
+    codec other than gzip it is ignored."""
     if record_type not in RECORD_TYPES:
         raise ValueError(
             f"Unsupported recordType {record_type!r} (expected one of {RECORD_TYPES})")
@@ -330,6 +376,7 @@ def write_tfrecord(data, path: str, record_type: str = "Example",
         schema = schema_from_arrow(table.schema)
     validate_schema_for_record_type(schema, record_type)
     eng = engine_mod.resolve_engine(engine)
+    gzip_device = _resolve_gzip_engine(gzip_engine, eng, codec)
 
     if record_type == "ByteArray":
         # reference: serializeByteArray frames column 0, which must be binary
@@ -376,14 +423,21 @@ def write_tfrecord(data, path: str, record_type: str = "Example",
             # pool (different files page-allocate concurrently; per-file
             # mmap registration would cost ~0.16 ms/MB each on the fresh
             # temp inodes — the r01 config-3 cliff)
-            view = gpu_engine.device_to_pinned_view(img)
+            view = (None if gzip_device
+                    else gpu_engine.device_to_pinned_view(img))
+
+            def _part_path(p):
+                return os.path.join(
+                    part_dir(combos[p]),
+                    P.part_file_name(shard_offset, codec, job_id))
 
             def _write_part(p, lo, hi):
-                sub_dir = part_dir(combos[p])
-                fpath = os.path.join(
-                    sub_dir, P.part_file_name(shard_offset, codec, job_id))
                 payload = (view[lo:hi] if codec is None
                            else P.compress_bytes(view[lo:hi].tobytes(), codec))
+                P.write_file_atomic(payload, _part_path(p))
+                return len(payload)
+
+            def _write_payload(payload, fpath):
                 P.write_file_atomic(payload, fpath)
                 return len(payload)
 
@@ -397,7 +451,23 @@ def write_tfrecord(data, path: str, record_type: str = "Example",
                 owner[tuple(_partition_dir_value(v) for v in combos[p])] = p
             ranges = [r for r in ranges if owner[tuple(
                 _partition_dir_value(v) for v in combos[r[0]])] == r[0]]
-            for nb in P.shared_pool().map(lambda a: _write_part(*a), ranges):
+            if gzip_device:
+                # each partition's slice of the device image compresses in
+                # HBM; its write overlaps the next partition's compression
+                # (two pinned buffers, as in the multi-shard path)
+                pool = P.shared_pool()
+                futs = []
+                for k, (p, lo, hi) in enumerate(ranges):
+                    if k >= 2:
+                        futs[k - 2].result()  # its pinned buffer is reused
+                    payload = _device_image_to_pinned(
+                        img[lo:hi], f"encw{k % 2}", True)
+                    futs.append(pool.submit(_write_payload, payload,
+                                            _part_path(p)))
+                sizes = [f.result() for f in futs]
+            else:
+                sizes = P.shared_pool().map(lambda a: _write_part(*a), ranges)
+            for nb in sizes:
                 if metrics is not None:
                     metrics.add(nbytes=nb, files=1)
             if metrics is not None:
@@ -410,10 +480,10 @@ def write_tfrecord(data, path: str, record_type: str = "Example",
                 sub = stripped.take(pa.array(idxs, type=pa.int64()))
                 _encode_and_write(sub, data_schema, record_type, part_dir(combo),
                                   codec, job_id, num_shards, shard_offset, eng,
-                                  metrics)
+                                  metrics, gzip_device)
     else:
         _encode_and_write(table, schema, record_type, path, codec, job_id,
-                          num_shards, shard_offset, eng, metrics)
+                          num_shards, shard_offset, eng, metrics, gzip_device)
 
     if write_success:
         P.write_success_marker(path)
