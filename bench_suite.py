@@ -15,6 +15,10 @@ driver runs it). This suite covers the rest, each printing one JSON line:
   gzip_write      GPU-engine gzip write, host zlib vs the device compressor
                   (gzip_engine="host" | "device"), on flagship-shaped
                   Example rows and on config 5's random ByteArray payloads
+  gzip_foreign    GPU-engine read of gzip files another program wrote (zlib
+                  level 6, no segment table): host zlib pool vs the
+                  speculative device inflater (foreign_gzip="host" |
+                  "device"), as one file and as 32 files
   gzip_bytearray  config 5: gzip-compressed ByteArray read, shard staged
                   through HBM on the GPU engine
 
@@ -335,9 +339,87 @@ def bench_gzip_write(args):
     shutil.rmtree(d, ignore_errors=True)
 
 
+def bench_gzip_foreign(args):
+    """GPU-engine read of foreign gzip (flagship-shaped Example frames
+    recompressed by zlib level 6 into plain gzip members): foreign_gzip=
+    "host" against "device", alternating in one process after a warm-up.
+    One file of --rows rows is single-stream latency; 32 files of --rows/32
+    are aggregate throughput."""
+    import zlib
+
+    import torch
+
+    import spark_tfrecord_amd as stf
+    from spark_tfrecord_amd.engine import gpu as gpu_engine
+    from spark_tfrecord_amd.io import paths as P
+
+    rank, world = _env_world()
+    if not torch.cuda.is_available():
+        raise SystemExit("gzip_foreign needs the GPU engine")
+    d = _workdir("gzf", rank)
+    for nfiles in (1, 32):
+        rows = max(args.rows // nfiles, 1) * nfiles
+        src = os.path.join(d, f"src{nfiles}")
+        stf.write_tfrecord(_flagship_table(rows, 3 + rank), src,
+                           record_type="Example", num_shards=nfiles,
+                           engine="gpu")
+        out = os.path.join(d, f"foreign{nfiles}")
+        os.makedirs(out)
+        raw_bytes = gz_bytes = 0
+        for k, f in enumerate(P.list_data_files(src)):
+            with open(f, "rb") as fh:
+                raw = fh.read()
+            co = zlib.compressobj(6, zlib.DEFLATED, 31)  # gzip wrapper
+            blob = co.compress(raw) + co.flush()
+            with open(os.path.join(out, f"part-{k:05d}.tfrecord.gz"),
+                      "wb") as fh:
+                fh.write(blob)
+            raw_bytes += len(raw)
+            gz_bytes += len(blob)
+        schema = stf.read_tfrecord(src, engine="gpu").schema
+        shutil.rmtree(src, ignore_errors=True)
+
+        def read(mode):
+            df = stf.read_tfrecord(out, schema=schema, engine="gpu",
+                                   foreign_gzip=mode)
+            torch.cuda.synchronize()
+            return df
+
+        el = {"host": 0.0, "device": 0.0}
+        live = []
+        for mode in el:
+            assert read(mode).count() == rows  # warm-up
+        for _ in range(args.reps):
+            for mode in el:
+                t0 = time.perf_counter()
+                read(mode)
+                el[mode] += time.perf_counter() - t0
+                if mode == "device":
+                    live = [e[1] for e in gpu_engine.last_foreign]
+        for mode, t in el.items():
+            dev = mode == "device"
+            _emit(rank, f"rows/sec foreign gzip read files={nfiles} "
+                        f"foreign_gzip={mode}",
+                  rows * args.reps / t, "rows/s",
+                  {"rows": rows, "files": nfiles, "foreign_gzip": mode,
+                   "raw_gb_per_s": round(raw_bytes * args.reps / t / 1e9, 4),
+                   "gz_bytes": gz_bytes, "raw_bytes": raw_bytes,
+                   # bytes over the host link per read: the compressed
+                   # files (device) or the inflated images (host) go up;
+                   # the decoded columns come down either way
+                   "h2d_bytes": gz_bytes if dev else raw_bytes,
+                   "live_chunks_per_file": (
+                       round(float(np.mean(live)), 1) if dev and live
+                       else None),
+                   "device_over_host": round(el["host"] / el["device"], 3),
+                   "engine": "gpu", "reps": args.reps}, t, 1)
+    shutil.rmtree(d, ignore_errors=True)
+
+
 BENCHES = {"plumbing": bench_plumbing, "partitionby": bench_partitionby,
            "infer": bench_infer, "gzip_bytearray": bench_gzip_bytearray,
-           "gzip_write": bench_gzip_write}
+           "gzip_write": bench_gzip_write,
+           "gzip_foreign": bench_gzip_foreign}
 
 
 def main():

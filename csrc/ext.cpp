@@ -31,6 +31,7 @@
 #include "codec_core.h"
 #include "deflate_core.h"
 #include "inflate_core.h"
+#include "inflate_spec_core.h"
 
 namespace py = pybind11;
 using namespace tfrec;
@@ -763,6 +764,32 @@ py::bytes host_inflate_segment(py::buffer comp, i64 expect) {
   return py::bytes(out);
 }
 
+// Host run of the block-parallel speculative inflater shared with the
+// gfx950 kernels (csrc/inflate_spec_core.h) over one whole gzip member.
+py::tuple host_inflate_foreign(py::buffer gz, i64 chunk_bytes) {
+  auto info = gz.request();
+  std::vector<u8> out;
+  tfrec::inflate::SpecStats st;
+  i64 err = tfrec::inflate::host_spec_inflate(
+      static_cast<const u8*>(info.ptr),
+      static_cast<i64>(info.size * info.itemsize), chunk_bytes, out, st);
+  if (err == -2)
+    throw std::runtime_error(
+        "host_inflate_foreign: not an eligible single gzip member");
+  if (err)
+    throw std::runtime_error("host_inflate_foreign rejected the stream: chunk " +
+                             std::to_string((err >> 8) - 1) + ", cause " +
+                             std::to_string(err & 0xFF));
+  py::dict stats;
+  stats["candidates"] = st.candidates;
+  stats["live_chunks"] = st.live;
+  stats["false_starts"] = st.false_starts;
+  stats["discarded"] = st.discarded;
+  stats["marker_symbols"] = st.markers;
+  return py::make_tuple(
+      py::bytes(reinterpret_cast<const char*>(out.data()), out.size()), stats);
+}
+
 // Host runs of the DEFLATE segment compressor core shared with the gfx950
 // kernel (csrc/deflate_core.h): `lane` < 0 emulates the lanes with loops and
 // is byte-identical to the device, which backs the CPU tests.
@@ -822,6 +849,7 @@ u32 masked_crc32c_py(py::buffer data) {
 void register_gpu(py::module_& m);      // defined in csrc/hip/kernels.hip
 void register_inflate(py::module_& m);  // defined in csrc/hip/inflate.hip
 void register_deflate(py::module_& m);  // defined in csrc/hip/deflate.hip
+void register_inflate_foreign(py::module_& m);  // csrc/hip/inflate_foreign.hip
 
 PYBIND11_MODULE(_native, m) {
   m.doc() = "MI355X-native TFRecord codec (host + gfx950 kernels)";
@@ -843,6 +871,10 @@ PYBIND11_MODULE(_native, m) {
   m.def("host_inflate_segment", &host_inflate_segment, py::arg("comp"),
         py::arg("expect"),
         "TEST-ONLY: run the device inflater's core on host for one segment");
+  m.def("host_inflate_foreign", &host_inflate_foreign, py::arg("gz"),
+        py::arg("chunk_bytes"),
+        "TEST-ONLY: run the speculative foreign-gzip inflater's core on host "
+        "over one member -> (bytes, stats); raises on a rejected stream");
   m.def("host_deflate_segment", &host_deflate_segment, py::arg("data"),
         py::arg("final"), py::arg("stored_threshold"),
         "TEST-ONLY: run the device compressor's core on host for one segment");
@@ -875,6 +907,7 @@ PYBIND11_MODULE(_native, m) {
   register_gpu(m);
   register_inflate(m);
   register_deflate(m);
+  register_inflate_foreign(m);
   m.attr("HAS_GPU_KERNELS") = true;
 #else
   m.attr("HAS_GPU_KERNELS") = false;

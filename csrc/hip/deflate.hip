@@ -28,6 +28,7 @@
 
 #include "../crc32c.h"
 #include "../deflate_core.h"
+#include "crc_wave.h"
 
 namespace py = pybind11;
 using namespace tfrec;
@@ -49,32 +50,6 @@ using tfrec::inflate::u64;
 using tfrec::inflate::u8;
 
 constexpr int kWavesPerBlock = 4;
-
-// CRC-32 of in[0, n) by one wave: each lane checksums a contiguous chunk
-// (all chunks but the last share one length, so one shift element serves
-// them), lane 0 folds the 64 values in order.
-__device__ inline u32 crc32_ieee_wave(const u8* __restrict__ in, i64 n,
-                                      int lane, u32* lds) {
-  i64 chunk = (((n + 63) / 64) + 7) & ~(i64)7;
-  i64 lo = (i64)lane * chunk;
-  if (lo > n) lo = n;
-  i64 hi = lo + chunk < n ? lo + chunk : n;
-  lds[lane] = crc32_ieee(in + lo, (size_t)(hi - lo));
-  TFR_WAVE_SYNC();
-  u32 acc = 0;
-  if (lane == 0 && n > 0) {
-    u32 full = crc32_ieee_shift_elem((u64)chunk);
-    for (int l = 0; l < 64; ++l) {
-      i64 a = (i64)l * chunk;
-      if (a >= n) break;
-      i64 len = a + chunk < n ? chunk : n - a;
-      u32 sh = len == chunk ? full : crc32_ieee_shift_elem((u64)len);
-      acc = crc_ieee_gfmul(acc, sh) ^ lds[l];
-    }
-  }
-  TFR_WAVE_SYNC();
-  return acc;  // valid on lane 0
-}
 
 // One segment per wave, grid-stride over segments. Segment i covers
 // in[i*seg, min(n, (i+1)*seg)) and writes its sub-stream to

@@ -334,6 +334,64 @@ TFR_HOSTDEV inline void bulk_copy(u8* dst, const u8* src, i64 n, int lane,
   TFR_WAVE_FENCE();  // other lanes may read these bytes (later matches)
 }
 
+// Dynamic-block header (RFC 1951 3.2.7), from HLIT on: the BFINAL/BTYPE
+// bits are already consumed. Leaves the hlit + hdist code lengths nibble-
+// packed in L.lens4 (distance lengths start at hlit); L.bc_dist, L.rank_dist
+// and the tail of L.sym are scratch for the code-length code. Returns 0 or
+// inflate_one's cause code. STRICT adds the tests a speculative block start
+// must pass (csrc/inflate_spec_core.h) and changes nothing else: a count
+// above the 286/30 symbols that exist, a code-length code that is not
+// complete, a repeat with nothing before it, a run past hlit + hdist.
+template <bool STRICT>
+TFR_HOSTDEV inline int parse_dyn_header(BitRd& br, LaneScratch& L, int& hlit,
+                                        int& hdist) {
+  hlit = (int)br_bits(br, 5) + 257;
+  hdist = (int)br_bits(br, 5) + 1;
+  int hclen = (int)br_bits(br, 4) + 4;
+  if (br.n < 0) return 5;
+  if (STRICT && (hlit > 286 || hdist > 30)) return 20;
+  // CL table borrows the tail of sym[] (lit/dist fills happen later)
+  uint16_t* cl_lens = &L.sym[300];  // 19 entries
+  uint16_t* cl_sym = &L.sym[280];   // <= 19 entries
+  for (int i = 0; i < 19; ++i) cl_lens[i] = 0;
+  u32 kraft = 0;
+  for (int i = 0; i < hclen; ++i) {
+    u32 l = br_bits(br, 3);
+    cl_lens[kClOrder[i]] = (uint16_t)l;
+    if (l) kraft += 128u >> l;
+  }
+  if (br.n < 0 || !build_huff16(cl_lens, 19, L.bc_dist, L.rank_dist, cl_sym))
+    return 6;
+  if (STRICT && kraft != 128u) return 21;
+  int total = hlit + hdist;
+  int n = 0;
+  u32 prev = 0;
+  while (n < total) {
+    int s = huff_decode(br, L.bc_dist, L.rank_dist, cl_sym);
+    if (s < 0) return 7;
+    if (s < 16) {
+      set_len4(L.lens4, n++, (u32)s);
+      prev = (u32)s;
+    } else {
+      int r;
+      u32 v = 0;
+      if (s == 16) {
+        if (STRICT && n == 0) return 22;
+        r = 3 + (int)br_bits(br, 2);
+        v = prev;
+      } else if (s == 17) {
+        r = 3 + (int)br_bits(br, 3);
+      } else {
+        r = 11 + (int)br_bits(br, 7);
+      }
+      if (STRICT && r > total - n) return 23;
+      while (r-- && n < total) set_len4(L.lens4, n++, v);
+    }
+    if (br.n < 0) return 8;
+  }
+  return 0;
+}
+
 // Inflate one raw-deflate segment into dst[0, expect). Returns 0 on
 // success, a small nonzero cause code otherwise (any nonzero => the Python
 // side redoes the FILE on the host zlib path). `in`/`dst` are __restrict__:
@@ -395,40 +453,9 @@ TFR_HOSTDEV inline int inflate_one(const u8* __restrict__ in, i64 ilen,
       for (int s = 280; s < 288; ++s) set_len4(L.lens4, s, 8);
       for (int s = 0; s < 32; ++s) set_len4(L.lens4, 288 + s, 5);
     } else {  // dynamic codes
-      hlit = (int)br_bits(br, 5) + 257;
-      hdist = (int)br_bits(br, 5) + 1;
-      int hclen = (int)br_bits(br, 4) + 4;
-      if (br.n < 0) return 5;
+      int rc = parse_dyn_header<false>(br, L, hlit, hdist);
+      if (rc) return rc;
       dist_off = hlit;
-      // CL table borrows the tail of sym[] (lit/dist fills happen later)
-      uint16_t* cl_lens = &L.sym[300];  // 19 entries
-      uint16_t* cl_sym = &L.sym[280];   // <= 19 entries
-      for (int i = 0; i < 19; ++i) cl_lens[i] = 0;
-      for (int i = 0; i < hclen; ++i) cl_lens[kClOrder[i]] = br_bits(br, 3);
-      if (br.n < 0 || !build_huff16(cl_lens, 19, L.bc_dist, L.rank_dist,
-                                    cl_sym))
-        return 6;
-      int total = hlit + hdist;
-      int n = 0;
-      u32 prev = 0;
-      while (n < total) {
-        int s = huff_decode(br, L.bc_dist, L.rank_dist, cl_sym);
-        if (s < 0) return 7;
-        if (s < 16) {
-          set_len4(L.lens4, n++, (u32)s);
-          prev = (u32)s;
-        } else if (s == 16) {
-          int r = 3 + (int)br_bits(br, 2);
-          while (r-- && n < total) set_len4(L.lens4, n++, prev);
-        } else if (s == 17) {
-          int r = 3 + (int)br_bits(br, 3);
-          while (r-- && n < total) set_len4(L.lens4, n++, 0);
-        } else {
-          int r = 11 + (int)br_bits(br, 7);
-          while (r-- && n < total) set_len4(L.lens4, n++, 0);
-        }
-        if (br.n < 0) return 8;
-      }
     }
     if (!build_huff4(L.lens4, 0, hlit, L.bc_lit, L.rank_lit, L.sym))
       return 9;

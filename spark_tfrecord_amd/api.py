@@ -116,6 +116,7 @@ class DataFrameReader(_OptionsMixin):
             schema=self._schema,
             record_type=self._options.get("recordtype", "Example"),
             engine=self._options.get("engine", "auto"),
+            foreign_gzip=self._options.get("foreigngzip"),
         )
 
 

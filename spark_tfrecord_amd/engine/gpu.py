@@ -1332,6 +1332,186 @@ def read_gzip_file_to_device(path: str, device="cuda") -> Optional[torch.Tensor]
     return data
 
 
+class ForeignGzipRejected(Exception):
+    """The device inflater refused some table-less gzip files of a group
+    (`paths`); the caller reads those through host zlib and redoes the
+    group without them."""
+
+    def __init__(self, paths):
+        super().__init__(f"device inflate rejected {len(paths)} gzip file(s)")
+        self.paths = list(paths)
+
+
+# what the last foreign-gzip inflate did, per file: [(path, live chunks,
+# marker symbols, error word)] — read by the tests and bench_suite.py
+last_foreign: list = []
+
+_FOREIGN_DEFAULT_CHUNK = 32 << 10
+_FOREIGN_MAX_FILES = 4096  # per launch (the CRC kernel's grid.y)
+
+
+def _foreign_chunk_bytes(chunk_bytes: Optional[int] = None) -> int:
+    """Compressed bytes per speculative chunk: the argument, else
+    TFREC_GZ_FOREIGN_CHUNK, else 32 KiB (zlib's level-6 blocks are about
+    that long compressed, so a finer stride finds no more block starts)."""
+    if chunk_bytes is None:
+        chunk_bytes = os.environ.get("TFREC_GZ_FOREIGN_CHUNK",
+                                     _FOREIGN_DEFAULT_CHUNK)
+    chunk_bytes = int(chunk_bytes)
+    if chunk_bytes < 64:
+        raise ValueError(
+            f"foreign gzip chunk stride must be >= 64 bytes, got {chunk_bytes}")
+    return chunk_bytes
+
+
+def foreign_gz_meta(path: str):
+    """(body_off, body_len, crc32, isize) of a gzip file from its header and
+    trailer alone, walking FEXTRA, FNAME, FCOMMENT and FHCRC (RFC 1952), or
+    None when the file is not for the device's speculative inflater: not
+    CM=8, shorter than 18 bytes, ISIZE 0, or a body of 4 GiB or more. Says
+    nothing about a segment table: gz_device_meta is asked first."""
+    if not getattr(_native, "HAS_GPU_KERNELS", False):
+        return None
+    try:
+        size = os.path.getsize(path)
+        if size < 18:
+            return None
+        with open(path, "rb") as f:
+            head = f.read(min(size, 128 << 10))  # FEXTRA <= 64 KiB + names
+            f.seek(size - 8)
+            trailer = f.read(8)
+    except OSError:
+        return None
+    return _foreign_gz_parse(head, trailer, size)
+
+
+def _foreign_gz_parse(head: bytes, trailer: bytes, size: int):
+    if head[:3] != b"\x1f\x8b\x08" or head[3] & 0xE0:
+        return None
+    flg = head[3]
+    pos = 10
+    if flg & 0x04:
+        if pos + 2 > len(head):
+            return None
+        pos += 2 + int.from_bytes(head[pos:pos + 2], "little")
+    for bit in (0x08, 0x10):  # FNAME, FCOMMENT: zero-terminated
+        if flg & bit:
+            end = head.find(b"\x00", pos)
+            if end < 0:
+                return None
+            pos = end + 1
+    if flg & 0x02:
+        pos += 2
+    body_len = size - 8 - pos
+    crc = int.from_bytes(trailer[:4], "little")
+    isize = int.from_bytes(trailer[4:], "little")
+    # DEFLATE cannot expand past 1032:1: a larger ISIZE belongs to another
+    # member or is damaged, and is not worth the buffers
+    if (pos > len(head) or body_len <= 0 or body_len >= (1 << 32)
+            or isize == 0 or isize > body_len * 1032 + 64):
+        return None
+    return pos, body_len, crc, isize
+
+
+def _device_inflate_foreign_group(data: torch.Tensor, items, device,
+                                  chunk_bytes: Optional[int] = None):
+    """Inflate table-less gzip files in HBM by block-parallel speculative
+    decode (csrc/hip/inflate_foreign.hip; the steps are laid out in
+    csrc/inflate_spec_core.h). items = [(path, foreign_gz_meta, out_base)];
+    each file's bytes land at data[out_base : out_base + isize]. All files
+    share every launch, the compressed bodies DMA from the page cache, and
+    the host waits once, for the per-file result words. The member CRC-32
+    is always checked: acceptance rests on a speculative chain, so nothing
+    but the checksum vouches for the bytes. Returns one bool per item;
+    False = refused (the slice's content is unspecified), read the file
+    through host zlib."""
+    chunk = _foreign_chunk_bytes(chunk_bytes)
+    CC, FC, RC = (_native.FOREIGN_CHUNK_COLS, _native.FOREIGN_FILE_COLS,
+                  _native.FOREIGN_RES_COLS)
+    piece = int(_native.FOREIGN_CRC_PIECE)
+    ok_all = []
+    del last_foreign[:]
+    main = torch.cuda.current_stream()
+    streams = _dma_streams()
+    for lo in range(0, len(items), _FOREIGN_MAX_FILES):
+        part = items[lo:lo + _FOREIGN_MAX_FILES]
+        nfile = len(part)
+        comp_sizes = [os.path.getsize(p) for p, _, _ in part]
+        comp_total = sum(comp_sizes)
+        comp = torch.empty(comp_total, dtype=torch.uint8, device=device)
+        ft = np.zeros((nfile, FC), np.int64)
+        coff = chunk0 = sym0 = piece0 = 0
+        used = []
+        for k, (p, meta, out_base) in enumerate(part):
+            body_off, body_len, crc, isize = meta
+            if (body_off + body_len + 8 != comp_sizes[k] or out_base < 0
+                    or out_base + isize > data.numel()):
+                raise ValueError(f"foreign gzip extents changed under the "
+                                 f"read: {p}")
+            ptr, pinned = _native.file_mmap_pinned(p, comp_sizes[k], False)
+            if pinned:
+                st = streams[k % len(streams)]
+                st.wait_stream(main)
+                _native.gpu_memcpy_h2d(comp.data_ptr() + coff, ptr,
+                                       comp_sizes[k], st.cuda_stream)
+                used.append(st)
+            else:
+                _read_file_staged(p, comp[coff:coff + comp_sizes[k]])
+            nchunk = -(-body_len // chunk)
+            ft[k, :9] = (coff + body_off, body_len, isize, crc, chunk0, nchunk,
+                         out_base, sym0, piece0)
+            coff += comp_sizes[k]
+            chunk0 += nchunk
+            sym0 += isize
+            piece0 += -(-isize // piece)
+        for st in set(used):
+            main.wait_stream(st)
+        # chunk table rows: file, start -1, len 0, end 0, next -2 (none),
+        # rc 0, out_off -1 (not live), live-list slot
+        ct = np.zeros((chunk0, CC), np.int64)
+        ct[:, 0] = np.repeat(np.arange(nfile), ft[:, 5])
+        ct[:, 1] = -1
+        ct[:, 4] = -2
+        ct[:, 6] = -1
+        res = np.zeros((nfile, RC), np.int64)
+        res[:, 0] = -1
+        ft_d = torch.as_tensor(ft).to(device)
+        ct_d = torch.as_tensor(ct).to(device)
+        res_d = torch.as_tensor(res).to(device)
+        sym = torch.empty(sym0, dtype=torch.int16, device=device)
+        piece_crc = torch.empty(piece0, dtype=torch.int32, device=device)
+        max_pieces = int((-(-ft[:, 2] // piece)).max())
+        _native.gpu_inflate_foreign(
+            comp.data_ptr(), ft_d.data_ptr(), ct_d.data_ptr(),
+            res_d.data_ptr(), piece_crc.data_ptr(), sym.data_ptr(),
+            data.data_ptr(), nfile, chunk0, max_pieces, chunk, _stream())
+        out = res_d.cpu().numpy()  # the one host wait
+        for k, (p, _, _) in enumerate(part):
+            ok_all.append(int(out[k, 0]) == -1)
+            last_foreign.append((p, int(out[k, 1]), int(out[k, 3]),
+                                 int(out[k, 0])))
+    return ok_all
+
+
+def read_foreign_gzip_file_to_device(path: str,
+                                     chunk_bytes: Optional[int] = None,
+                                     device="cuda") -> Optional[torch.Tensor]:
+    """Any single-member gzip file -> decompressed bytes in HBM via the
+    speculative device inflater, CRC-32 checked. None when the file is not
+    eligible (foreign_gz_meta) or the inflater refused it: multi-member,
+    truncated, corrupt, CRC or ISIZE mismatch (callers fall back to host
+    zlib)."""
+    check_native()
+    meta = foreign_gz_meta(path)
+    if meta is None:
+        return None
+    data = torch.empty(meta[3], dtype=torch.uint8, device=device)
+    if not _device_inflate_foreign_group(data, [(path, meta, 0)], device,
+                                         chunk_bytes)[0]:
+        return None
+    return data
+
+
 def _deflate_max_waves(device) -> int:
     """Resident-wave cap of the compressor launch: its token workspace is
     sized per resident wave (4 B per input byte of one segment), not per
@@ -1394,30 +1574,41 @@ def gzip_image_device(img: torch.Tensor, seg: Optional[int] = None) -> torch.Ten
 
 
 def read_files_to_batch(paths, schema: StructType, record_type: str,
-                        verify_crc: bool = True, device="cuda"):
+                        verify_crc: bool = True, device="cuda",
+                        foreign_gzip: bool = False):
     """Decode MANY files as ONE GPU pipeline: their (decompressed) images
     are concatenated in HBM (TFRecord frames are concatenable, so the frame
     chain spans file boundaries exactly), scanned and decoded once, and the
     per-file row counts recovered with a searchsorted over frame offsets.
     Uncompressed files DMA straight from the page cache; gzip files bearing
     our segment table are inflated by the device inflater (all files'
-    segments in one launch). Returns (device RecordBatch, np.ndarray
-    row_counts per file)."""
+    segments in one launch). With `foreign_gzip`, gzip files without the
+    table go through the speculative inflater into their own slices of the
+    same image; if it refuses any, ForeignGzipRejected names them and
+    nothing is decoded. Returns (device RecordBatch, np.ndarray row_counts
+    per file)."""
     from ..io import paths as P
 
     check_native()
     metas = []
+    fmetas = []
     sizes = []
     for p in paths:
         if P.codec_from_path(p) == "gzip":
             meta = P.parse_gz_segments_file(p)
-            if meta is None:
+            fmeta = None
+            if meta is None and foreign_gzip:
+                fmeta = foreign_gz_meta(p)
+            if meta is None and fmeta is None:
                 raise ValueError(f"gzip file without segment table: {p} "
                                  "(host path required)")
             metas.append(meta)
-            sizes.append(sum(u for _, u in meta[1]))
+            fmetas.append(fmeta)
+            sizes.append(sum(u for _, u in meta[1]) if meta is not None
+                         else fmeta[3])
         else:
             metas.append(None)
+            fmetas.append(None)
             sizes.append(os.path.getsize(p))
     n = sum(sizes)
     if n == 0:
@@ -1434,11 +1625,15 @@ def read_files_to_batch(paths, schema: StructType, record_type: str,
     main = torch.cuda.current_stream()
     streams = _dma_streams()
     gz_items = []
+    foreign_items = []
     for i, p in enumerate(paths):
         if not sizes[i]:
             continue
         if metas[i] is not None:
             gz_items.append((p, metas[i], int(bounds[i])))
+            continue
+        if fmetas[i] is not None:
+            foreign_items.append((p, fmetas[i], int(bounds[i])))
             continue
         ptr, pinned = _native.file_mmap_pinned(p, sizes[i], False)
         if pinned:
@@ -1448,6 +1643,13 @@ def read_files_to_batch(paths, schema: StructType, record_type: str,
             main.wait_stream(st)
         else:
             _read_file_staged(p, data[int(bounds[i]):int(bounds[i + 1])])
+    if foreign_items:
+        ok = _device_inflate_foreign_group(data, foreign_items, device)
+        refused = [it[0] for it, good in zip(foreign_items, ok) if not good]
+        if refused:
+            # a refused file's true length is unknown (its ISIZE may be
+            # another member's), so the image layout cannot be kept
+            raise ForeignGzipRejected(refused)
     if gz_items and not _device_inflate_group(data, gz_items, device):
         # rare fallback: a segment the kernel rejected — host zlib fills
         # the affected files' slices

@@ -32,6 +32,29 @@ from . import paths as P
 
 __all__ = ["read_tfrecord", "infer_schema_of_paths"]
 
+FOREIGN_GZIP_MODES = ("host", "device")
+
+
+def _resolve_foreign_gzip(foreign_gzip: Optional[str], eng: str) -> bool:
+    """True when gzip files WITHOUT our segment table (any other writer's)
+    are inflated in HBM by the speculative inflater
+    (csrc/hip/inflate_foreign.hip) instead of by host zlib. None = the
+    default: "host", or what TFREC_GZ_FOREIGN says for GPU-engine reads."""
+    explicit = foreign_gzip is not None
+    if not explicit:
+        foreign_gzip = (os.environ.get("TFREC_GZ_FOREIGN", "host")
+                        if eng == "gpu" else "host")
+    val = str(foreign_gzip).lower()
+    if val not in FOREIGN_GZIP_MODES:
+        raise ValueError(
+            f"Unsupported foreign gzip mode {foreign_gzip!r} (expected one "
+            f"of {FOREIGN_GZIP_MODES})")
+    if val == "device" and eng != "gpu":
+        raise ValueError(
+            'foreign_gzip="device" needs the GPU engine; this read resolved '
+            f"to engine={eng!r}")
+    return val == "device"
+
 
 def _load_file(path: str) -> np.ndarray:
     return np.frombuffer(P.decompress_file(path), np.uint8)
@@ -148,8 +171,14 @@ def count_tfrecord(path: str, engine: str = "auto") -> int:
 def read_tfrecord(path: str, schema: Optional[StructType] = None,
                   record_type: str = "Example", engine: str = "auto",
                   verify_crc: bool = True, base_dir: Optional[str] = None,
-                  columns: Optional[List[str]] = None):
+                  columns: Optional[List[str]] = None,
+                  foreign_gzip: Optional[str] = None):
     """Read a TFRecord dataset as a DataFrame.
+
+    `foreign_gzip` "device" inflates gzip files that other programs wrote
+    (no segment table) on the GPU, "host" (the default, or TFREC_GZ_FOREIGN)
+    leaves them to host zlib; a file the device refuses is read on the host
+    either way.
 
     `columns` projects the read: only the named fields are scanned and
     extracted (the schema-driven kernels skip other features entirely, like
@@ -169,6 +198,8 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
             base_dir = path if os.path.isdir(path) else os.path.dirname(path)
     part_cols = _partition_schema(files, base_dir) if base_dir else []
     eng = engine_mod.resolve_engine(engine)
+    foreign_device = _resolve_foreign_gzip(foreign_gzip, eng)
+    host_only: set = set()  # foreign gzip files the device refused
 
     metrics = IOMetrics("read")
 
@@ -179,7 +210,16 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
     # bounds resident decompressed bytes.
     from concurrent.futures import ThreadPoolExecutor
 
+    _host_bytes_memo: dict = {}
+
     def _needs_host_bytes(fpath: str) -> bool:
+        if fpath in host_only:
+            return True
+        if fpath not in _host_bytes_memo:  # asked several times per file
+            _host_bytes_memo[fpath] = _needs_host_bytes_uncached(fpath)
+        return _host_bytes_memo[fpath]
+
+    def _needs_host_bytes_uncached(fpath: str) -> bool:
         if eng != "gpu":
             return True
         codec = P.codec_from_path(fpath)
@@ -189,7 +229,12 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
             # our gzip files carry a segment table: the device inflater
             # decompresses them in HBM (foreign gzip stays on host zlib)
             from ..engine import gpu as gpu_engine
-            return gpu_engine.gz_device_meta(fpath) is None
+            if gpu_engine.gz_device_meta(fpath) is not None:
+                return False
+            # any other writer's gzip: the speculative inflater, if asked
+            # for and the file is eligible
+            return not (foreign_device
+                        and gpu_engine.foreign_gz_meta(fpath) is not None)
         return True
 
     # Schema-less GPU reads DEFER inference into the first group pipeline:
@@ -272,30 +317,51 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
 
                 group = []
                 gbytes = 0
+                i0 = i
                 while (i < len(files) and not _needs_host_bytes(files[i])
                        and gbytes < _GROUP_BYTES):
                     group.append(files[i])
-                    sz = os.path.getsize(files[i])
-                    gbytes += sz
-                    metrics.add(files=1, nbytes=sz)
+                    gbytes += os.path.getsize(files[i])
                     i += 1
-                if data_schema is None:
-                    try:
-                        batch, row_counts = gpu_engine.read_files_to_batch(
-                            group, None, record_type, verify_crc=verify_crc)
-                        data_schema = _resolve(batch.schema)
-                    except ValueError:
-                        # this group was entirely empty: resolve the schema
-                        # from the full file list, then decode normally
-                        data_schema = _resolve(
-                            byte_array_schema() if record_type == "ByteArray"
-                            else infer_schema_of_paths(files, record_type, eng))
+                try:
+                    if data_schema is None:
+                        try:
+                            batch, row_counts = gpu_engine.read_files_to_batch(
+                                group, None, record_type,
+                                verify_crc=verify_crc,
+                                foreign_gzip=foreign_device)
+                            data_schema = _resolve(batch.schema)
+                        except ValueError:
+                            # this group was entirely empty: resolve the
+                            # schema from the full file list, then decode
+                            # normally
+                            data_schema = _resolve(
+                                byte_array_schema()
+                                if record_type == "ByteArray"
+                                else infer_schema_of_paths(files, record_type,
+                                                           eng))
+                            batch, row_counts = gpu_engine.read_files_to_batch(
+                                group, data_schema, record_type,
+                                verify_crc=verify_crc,
+                                foreign_gzip=foreign_device)
+                    else:
                         batch, row_counts = gpu_engine.read_files_to_batch(
                             group, data_schema, record_type,
-                            verify_crc=verify_crc)
-                else:
-                    batch, row_counts = gpu_engine.read_files_to_batch(
-                        group, data_schema, record_type, verify_crc=verify_crc)
+                            verify_crc=verify_crc, foreign_gzip=foreign_device)
+                except gpu_engine.ForeignGzipRejected as rej:
+                    # redo the group without the refused files: they take
+                    # the host path, as with foreign_gzip="host"
+                    import logging
+
+                    for p in rej.paths:
+                        logging.getLogger(__name__).warning(
+                            "device inflate refused foreign gzip file %s; "
+                            "host zlib fallback", p)
+                    host_only.update(rej.paths)
+                    i = i0
+                    continue
+                for f in group:
+                    metrics.add(files=1, nbytes=os.path.getsize(f))
                 if batch.num_rows == 0 and not part_cols:
                     continue
                 t = batch_to_table(gpu_engine.batch_to_host(batch))
@@ -310,6 +376,12 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
                         and j not in futures):
                     futures[j] = _pool().submit(_host_task, files[j])
             metrics.add(files=1, nbytes=os.path.getsize(fpath))
+            if data_schema is None:
+                # inference was deferred to a group the device then refused
+                with StageTimer(metrics, "infer_schema"):
+                    data_schema = _resolve(
+                        byte_array_schema() if record_type == "ByteArray"
+                        else infer_schema_of_paths(files, record_type, eng))
             got = _blob(i)
             i += 1
             if eng == "gpu":

@@ -82,7 +82,7 @@ class TFRecordIterableDataset(torch.utils.data.IterableDataset):
                  columns: Optional[Sequence[str]] = None,
                  engine: str = "auto", verify_crc: bool = True,
                  shuffle_files: bool = False, seed: int = 0,
-                 prefetch: int = 1):
+                 prefetch: int = 1, foreign_gzip: Optional[str] = None):
         super().__init__()
         self.path = path
         self.record_type = record_type
@@ -93,6 +93,16 @@ class TFRecordIterableDataset(torch.utils.data.IterableDataset):
         self.shuffle_files = shuffle_files
         self.seed = seed
         self.prefetch = int(prefetch)  # shards decoded ahead (0 = sync)
+        # "device": other writers' gzip shards inflate on the GPU too
+        # (read_tfrecord's option of the same name); checked here, resolved
+        # against the engine in __iter__
+        if foreign_gzip is not None:
+            from .io.reader import FOREIGN_GZIP_MODES
+            if str(foreign_gzip).lower() not in FOREIGN_GZIP_MODES:
+                raise ValueError(
+                    f"Unsupported foreign gzip mode {foreign_gzip!r} "
+                    f"(expected one of {FOREIGN_GZIP_MODES})")
+        self.foreign_gzip = foreign_gzip
         files = P.list_data_files(path)
         if not files:
             raise FileNotFoundError(f"No TFRecord files found under {path}")
@@ -125,6 +135,8 @@ class TFRecordIterableDataset(torch.utils.data.IterableDataset):
             files = files[info.id::info.num_workers]
         return files
 
+    _foreign_device = False
+
     def _decode_one(self, fpath: str, eng: str, sub_schema):
         if os.path.getsize(fpath) == 0:
             return None
@@ -138,6 +150,10 @@ class TFRecordIterableDataset(torch.utils.data.IterableDataset):
             # our gzip shards inflate ON the training GPU (segment table)
             from .engine import gpu as gpu_engine
             dev = gpu_engine.read_gzip_file_to_device(fpath)
+            if dev is None and self._foreign_device:
+                # no segment table: the speculative inflater (None again
+                # for a file it refuses -> host zlib below)
+                dev = gpu_engine.read_foreign_gzip_file_to_device(fpath)
             if dev is not None:
                 if dev.numel() == 0:
                     return None
@@ -156,6 +172,8 @@ class TFRecordIterableDataset(torch.utils.data.IterableDataset):
 
     def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
         eng = engine_mod.resolve_engine(self.engine)
+        from .io.reader import _resolve_foreign_gzip
+        self._foreign_device = _resolve_foreign_gzip(self.foreign_gzip, eng)
         fields = [f for f in self.schema.fields
                   if self.columns is None or f.name in self.columns]
         sub_schema = StructType(fields)
