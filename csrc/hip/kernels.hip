@@ -439,8 +439,14 @@ __device__ inline i64 wave_incl_scan(i64 v) {
 // owns the values STARTING in its contiguous chunk (a varint may spill into
 // the next lane's chunk — reads cross, ownership doesn't). Returns the
 // total value count (uniform across the wave).
+// The count pass only counts terminator bytes, so a varint with no
+// terminator within 10 bytes (or before the run ends) is first seen here:
+// like read_varint it is refused, never cut after ten bytes and resumed as
+// if a new varint started at the eleventh. *bad comes back wave-uniform,
+// and no lane stores past the `total` slots the terminators account for.
 __device__ inline i64 wave_extract_i64_packed(const u8* __restrict__ p, i64 n,
-                                              i64* __restrict__ out, i64 base) {
+                                              i64* __restrict__ out, i64 base,
+                                              bool* bad) {
   int lane = threadIdx.x & 63;
   i64 chunk = (n + 63) / 64;
   i64 lo = (i64)lane * chunk;
@@ -463,19 +469,31 @@ __device__ inline i64 wave_extract_i64_packed(const u8* __restrict__ p, i64 n,
     }
   }
   i64 idx = base + excl + pre;
+  i64 idx_end = base + total;
+  bool overlong = false;
   while (q < hi) {
     u64 v = 0;
     int shift = 0;
     i64 j = q;
+    bool terminated = false;
     while (j < n && shift < 70) {
       u8 b = p[j++];
       v |= (u64)(b & 0x7F) << shift;
       shift += 7;
-      if (!(b & 0x80)) break;
+      if (!(b & 0x80)) {
+        terminated = true;
+        break;
+      }
     }
-    out[idx++] = (i64)v;
+    if (!terminated) {
+      overlong = true;
+      break;
+    }
+    if (idx < idx_end) out[idx] = (i64)v;
+    ++idx;
     q = j;
   }
+  *bad = __any(overlong) != 0;
   return total;
 }
 
@@ -530,7 +548,9 @@ __device__ inline int32_t extract_list_body_wave(const u8* __restrict__ p,
         u64 len;
         p = read_varint(p, end, &len);
         if (!p || (u64)(end - p) < len) return ERR_TRUNCATED;
-        *vi += wave_extract_i64_packed(p, (i64)len, dst.i64_vals, *vi);
+        bool bad;
+        *vi += wave_extract_i64_packed(p, (i64)len, dst.i64_vals, *vi, &bad);
+        if (bad) return ERR_BAD_VARINT;
         p += len;
       } else {
         u64 v;
