@@ -416,10 +416,80 @@ def bench_gzip_foreign(args):
     shutil.rmtree(d, ignore_errors=True)
 
 
+def bench_snappy(args):
+    """GPU-engine read of --rows flagship Example rows written once with
+    codec="snappy" (8 shards): the device Snappy decoder against
+    TFREC_SNAPPY=host (pyarrow on the host), and against the same rows as
+    own-format gzip through the device inflater. The three alternate in one
+    process after a warm-up."""
+    import torch
+
+    import spark_tfrecord_amd as stf
+    from spark_tfrecord_amd.engine import gpu as gpu_engine
+    from spark_tfrecord_amd.io import paths as P
+
+    rank, world = _env_world()
+    if not torch.cuda.is_available():
+        raise SystemExit("snappy needs the GPU engine")
+    rows = args.rows
+    d = _workdir("snp", rank)
+    table = _flagship_table(rows, 5 + rank)
+    dirs = {}
+    sizes = {}
+    for codec in ("snappy", "gzip"):
+        dirs[codec] = os.path.join(d, codec)
+        stf.write_tfrecord(table, dirs[codec], record_type="Example",
+                           codec=codec, num_shards=8, engine="gpu")
+        sizes[codec] = sum(os.path.getsize(f)
+                           for f in P.list_data_files(dirs[codec]))
+    schema = stf.read_tfrecord(dirs["snappy"], engine="gpu").schema
+    del table
+    modes = {"snappy device": ("snappy", "device"),
+             "snappy host": ("snappy", "host"),
+             "gzip device": ("gzip", "device")}
+
+    def read(mode):
+        codec, knob = modes[mode]
+        os.environ["TFREC_SNAPPY"] = knob
+        del gpu_engine.last_snappy[:]
+        df = stf.read_tfrecord(dirs[codec], schema=schema, engine="gpu")
+        torch.cuda.synchronize()
+        assert bool(gpu_engine.last_snappy) == (mode == "snappy device")
+        return df
+
+    el = dict.fromkeys(modes, 0.0)
+    chunks = 0
+    for mode in modes:
+        assert read(mode).count() == rows  # warm-up
+    for _ in range(args.reps):
+        for mode in modes:
+            t0 = time.perf_counter()
+            read(mode)
+            el[mode] += time.perf_counter() - t0
+            if mode == "snappy device":
+                chunks = sum(e[1] for e in gpu_engine.last_snappy)
+    os.environ.pop("TFREC_SNAPPY", None)
+    for mode, t in el.items():
+        codec = modes[mode][0]
+        _emit(rank, f"rows/sec read {mode}", rows * args.reps / t, "rows/s",
+              {"rows": rows, "files": 8, "mode": mode,
+               "file_bytes": sizes[codec],
+               "snappy_over_gzip_bytes": round(
+                   sizes["snappy"] / sizes["gzip"], 3),
+               "snappy_chunks": chunks if mode == "snappy device" else None,
+               "device_over_host": round(
+                   el["snappy host"] / el["snappy device"], 3),
+               "device_snappy_over_device_gzip": round(
+                   el["gzip device"] / el["snappy device"], 3),
+               "engine": "gpu", "reps": args.reps}, t, 1)
+    shutil.rmtree(d, ignore_errors=True)
+
+
 BENCHES = {"plumbing": bench_plumbing, "partitionby": bench_partitionby,
            "infer": bench_infer, "gzip_bytearray": bench_gzip_bytearray,
            "gzip_write": bench_gzip_write,
-           "gzip_foreign": bench_gzip_foreign}
+           "gzip_foreign": bench_gzip_foreign,
+           "snappy": bench_snappy}
 
 
 def main():

@@ -18,7 +18,8 @@ OUT = ROOT / "spark_tfrecord_amd" / "_native.so"
 SOURCES = [ROOT / "csrc" / "ext.cpp", ROOT / "csrc" / "hip" / "kernels.hip",
            ROOT / "csrc" / "hip" / "inflate.hip",
            ROOT / "csrc" / "hip" / "deflate.hip",
-           ROOT / "csrc" / "hip" / "inflate_foreign.hip"]
+           ROOT / "csrc" / "hip" / "inflate_foreign.hip",
+           ROOT / "csrc" / "hip" / "snappy.hip"]
 HEADERS = list((ROOT / "csrc").rglob("*.h"))
 
 

@@ -32,6 +32,7 @@
 #include "deflate_core.h"
 #include "inflate_core.h"
 #include "inflate_spec_core.h"
+#include "snappy_core.h"
 
 namespace py = pybind11;
 using namespace tfrec;
@@ -812,6 +813,23 @@ py::bytes host_deflate_segment(py::buffer data, bool final,
   return py::bytes(out.data(), static_cast<size_t>(len));
 }
 
+// Host run of the raw-Snappy chunk decoder core shared with the gfx950
+// kernel (csrc/snappy_core.h): `lane` < 0 does the lanes' share with loops
+// and is byte-identical to the device, which backs the CPU tests.
+py::bytes host_unsnap_chunk(py::buffer comp, i64 expect_len) {
+  auto info = comp.request();
+  if (expect_len < 0)
+    throw std::invalid_argument("host_unsnap_chunk: expect_len < 0");
+  std::string out(static_cast<size_t>(expect_len), '\0');
+  int rc = tfrec::snappy::unsnap_one(
+      static_cast<const u8*>(info.ptr),
+      static_cast<i64>(info.size * info.itemsize),
+      reinterpret_cast<u8*>(&out[0]), expect_len);
+  if (rc)
+    throw std::runtime_error("unsnap_one failed: cause " + std::to_string(rc));
+  return py::bytes(out);
+}
+
 std::vector<int> host_huffman_lengths(const std::vector<u32>& freqs,
                                       int max_len) {
   if (freqs.size() > 288 || max_len < 1 || max_len > 15)
@@ -850,6 +868,7 @@ void register_gpu(py::module_& m);      // defined in csrc/hip/kernels.hip
 void register_inflate(py::module_& m);  // defined in csrc/hip/inflate.hip
 void register_deflate(py::module_& m);  // defined in csrc/hip/deflate.hip
 void register_inflate_foreign(py::module_& m);  // csrc/hip/inflate_foreign.hip
+void register_snappy(py::module_& m);   // defined in csrc/hip/snappy.hip
 
 PYBIND11_MODULE(_native, m) {
   m.doc() = "MI355X-native TFRecord codec (host + gfx950 kernels)";
@@ -878,6 +897,10 @@ PYBIND11_MODULE(_native, m) {
   m.def("host_deflate_segment", &host_deflate_segment, py::arg("data"),
         py::arg("final"), py::arg("stored_threshold"),
         "TEST-ONLY: run the device compressor's core on host for one segment");
+  m.def("host_unsnap_chunk", &host_unsnap_chunk, py::arg("comp"),
+        py::arg("expect_len"),
+        "TEST-ONLY: run the device Snappy decoder's core on host for one raw "
+        "chunk; raises RuntimeError naming the cause code on a refusal");
   m.def("host_huffman_lengths", &host_huffman_lengths, py::arg("freqs"),
         py::arg("max_len"),
         "TEST-ONLY: length-limited Huffman code lengths of the compressor core");
@@ -908,6 +931,7 @@ PYBIND11_MODULE(_native, m) {
   register_inflate(m);
   register_deflate(m);
   register_inflate_foreign(m);
+  register_snappy(m);
   m.attr("HAS_GPU_KERNELS") = true;
 #else
   m.attr("HAS_GPU_KERNELS") = false;

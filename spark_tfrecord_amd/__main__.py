@@ -4,7 +4,7 @@
     schema   PATH [--record-type T]  inferred schema
     validate PATH                    CRC-check every frame of every file
     head     PATH [-n N]             first N records as JSON lines
-    convert  SRC DST [--codec C]     re-encode a dataset (e.g. gzip <-> plain)
+    convert  SRC DST [--codec C]     re-encode a dataset (gzip, deflate, snappy, plain)
 """
 
 import argparse

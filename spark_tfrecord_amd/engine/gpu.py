@@ -1332,14 +1332,33 @@ def read_gzip_file_to_device(path: str, device="cuda") -> Optional[torch.Tensor]
     return data
 
 
-class ForeignGzipRejected(Exception):
+class DeviceDecompressRejected(Exception):
+    """A device decompressor refused some files of a group (`paths`); the
+    caller reads those through the host codec and redoes the group without
+    them."""
+
+    def __init__(self, paths, message):
+        super().__init__(message)
+        self.paths = list(paths)
+
+
+class ForeignGzipRejected(DeviceDecompressRejected):
     """The device inflater refused some table-less gzip files of a group
     (`paths`); the caller reads those through host zlib and redoes the
     group without them."""
 
     def __init__(self, paths):
-        super().__init__(f"device inflate rejected {len(paths)} gzip file(s)")
-        self.paths = list(paths)
+        super().__init__(
+            paths, f"device inflate rejected {len(paths)} gzip file(s)")
+
+
+class SnappyRejected(DeviceDecompressRejected):
+    """The device Snappy decoder refused a chunk of some `.snappy` files of
+    a group (`paths`); the caller reads those on the host."""
+
+    def __init__(self, paths):
+        super().__init__(
+            paths, f"device snappy decode rejected {len(paths)} file(s)")
 
 
 # what the last foreign-gzip inflate did, per file: [(path, live chunks,
@@ -1512,6 +1531,154 @@ def read_foreign_gzip_file_to_device(path: str,
     return data
 
 
+# what the last device Snappy decode did, per file: [(path, chunks, error
+# word)] — read by the tests and bench_suite.py
+last_snappy: list = []
+
+# Largest raw chunk the device takes. One wave walks one chunk's elements
+# serially, so a long chunk holds one wave while the rest of the card
+# idles; 1 MiB covers Hadoop's default 256 KiB buffer (and four times it)
+# and keeps the slowest wave's walk in the low milliseconds. A file with a
+# longer chunk is read on the host.
+SNAPPY_MAX_CHUNK_RAW = 1 << 20
+
+
+def snappy_on_device() -> bool:
+    """TFREC_SNAPPY=device|host: where GPU-engine reads decompress
+    `.snappy` files (default device; host = pyarrow's Snappy)."""
+    val = os.environ.get("TFREC_SNAPPY", "device").lower()
+    if val not in ("device", "host"):
+        raise ValueError(
+            f"Unsupported TFREC_SNAPPY {val!r} (expected 'device' or 'host')")
+    return val == "device"
+
+
+def snappy_device_meta(path: str):
+    """(chunk extents, total raw size) of a `.snappy` file from its block
+    headers alone (io/paths.py snappy_walk over a read-only mmap: 8 header
+    bytes and a length preamble per block, the bodies stay untouched), or
+    None when the file is not for the device decoder: TFREC_SNAPPY=host, a
+    malformed container, or a chunk above SNAPPY_MAX_CHUNK_RAW. The
+    extents are an int64 array of rows (in_off, in_len, out_off, out_len).
+    Gates the device read path; None sends the file to the host."""
+    import mmap
+
+    from ..io import paths as P
+
+    if not getattr(_native, "HAS_GPU_KERNELS", False) or not snappy_on_device():
+        return None
+    try:
+        size = os.path.getsize(path)
+        if size == 0:
+            return np.zeros((0, 4), np.int64), 0
+        with open(path, "rb") as f:
+            with mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+                chunks, total = P.snappy_walk(mm, path)
+    except (OSError, ValueError):
+        return None
+    ext = np.array(chunks, np.int64).reshape(-1, 4)
+    if ext.shape[0] and int(ext[:, 3].max()) > SNAPPY_MAX_CHUNK_RAW:
+        return None
+    return ext, total
+
+
+def _snappy_max_waves(device) -> int:
+    """Grid cap of the Snappy launch, in waves: 16 per CU. The kernel is
+    bound by the latency of each element's copy, not by bandwidth, so more
+    resident waves are more throughput: 1M flagship rows (3288 chunks) took
+    5.75 ms at 8 per CU (two rounds of the grid-stride loop) and 3.61 ms at
+    16, 24 or 28, where every chunk has a wave (profiles/RESULTS.md). More
+    chunks than the cap take the kernel's grid-stride loop."""
+    return 16 * torch.cuda.get_device_properties(device).multi_processor_count
+
+
+def _device_unsnap_group(data: torch.Tensor, items, device):
+    """Decode several `.snappy` files in HBM in ONE launch, one raw chunk
+    per wave (csrc/hip/snappy.hip), each file's bytes landing at
+    data[out_base : out_base + total]. items = [(path, snappy_device_meta,
+    out_base)]. The compressed files DMA from the page cache (pinned mmaps)
+    on the side streams, the chunk table is checked against both buffers
+    here before it is uploaded, and the host waits once, for the per-file
+    error words. Returns one bool per item; False = a chunk was refused
+    (the slice's content is unspecified), read the file on the host."""
+    del last_snappy[:]
+    nfile = len(items)
+    comp_sizes = [os.path.getsize(p) for p, _, _ in items]
+    comp_total = sum(comp_sizes)
+    comp = torch.empty(max(comp_total, 1), dtype=torch.uint8,
+                       device=device)[:comp_total]
+    main = torch.cuda.current_stream()
+    streams = _dma_streams()
+    tables = []
+    chunk0 = np.zeros(nfile, np.int64)
+    coff = nchunk = 0
+    used = []
+    for k, (p, meta, out_base) in enumerate(items):
+        ext, total = meta
+        chunk0[k] = nchunk
+        if ext.shape[0]:
+            t = np.empty((ext.shape[0], 5), np.int64)
+            t[:, 0] = ext[:, 0] + coff
+            t[:, 1] = ext[:, 1]
+            t[:, 2] = ext[:, 2] + out_base
+            t[:, 3] = ext[:, 3]
+            t[:, 4] = k
+            # every extent inside its own file's slice of both buffers
+            if (ext[:, 0].min() < 0 or ext[:, 1].min() < 0
+                    or (ext[:, 0] + ext[:, 1]).max() > comp_sizes[k]
+                    or ext[:, 2].min() < 0 or ext[:, 3].min() < 0
+                    or (ext[:, 2] + ext[:, 3]).max() > total
+                    or out_base < 0 or out_base + total > data.numel()):
+                raise ValueError(f"snappy extents changed under the read: {p}")
+            tables.append(t)
+            nchunk += ext.shape[0]
+        if comp_sizes[k]:
+            ptr, pinned = _native.file_mmap_pinned(p, comp_sizes[k], False)
+            if pinned:
+                st = streams[k % len(streams)]
+                st.wait_stream(main)
+                _native.gpu_memcpy_h2d(comp.data_ptr() + coff, ptr,
+                                       comp_sizes[k], st.cuda_stream)
+                used.append(st)
+            else:
+                _read_file_staged(p, comp[coff:coff + comp_sizes[k]])
+        coff += comp_sizes[k]
+    for st in set(used):
+        main.wait_stream(st)
+    err = np.full(nfile, -1, np.int64)
+    if nchunk:
+        assert int(_native.SNAPPY_CHUNK_COLS) == 5
+        ct_d = torch.as_tensor(np.concatenate(tables)).to(device)
+        c0_d = torch.as_tensor(chunk0).to(device)
+        err_d = torch.as_tensor(err).to(device)
+        _native.gpu_unsnap_chunks(
+            comp.data_ptr(), ct_d.data_ptr(), c0_d.data_ptr(), nchunk,
+            data.data_ptr(), err_d.data_ptr(), _snappy_max_waves(device),
+            _stream())
+        err = err_d.cpu().numpy()  # the one host wait
+    ok = []
+    for k, (p, meta, _) in enumerate(items):
+        ok.append(int(err[k]) == -1)
+        last_snappy.append((p, int(meta[0].shape[0]), int(err[k])))
+    return ok
+
+
+def read_snappy_file_to_device(path: str,
+                               device="cuda") -> Optional[torch.Tensor]:
+    """`.snappy` file -> decompressed bytes in HBM via the device decoder.
+    None when the file is not eligible (snappy_device_meta) or the kernel
+    refused a chunk (callers fall back to the host codec)."""
+    check_native()
+    meta = snappy_device_meta(path)
+    if meta is None:
+        return None
+    total = meta[1]
+    data = torch.empty(max(total, 1), dtype=torch.uint8, device=device)[:total]
+    if not _device_unsnap_group(data, [(path, meta, 0)], device)[0]:
+        return None
+    return data
+
+
 def _deflate_max_waves(device) -> int:
     """Resident-wave cap of the compressor launch: its token workspace is
     sized per resident wave (4 B per input byte of one segment), not per
@@ -1582,7 +1749,9 @@ def read_files_to_batch(paths, schema: StructType, record_type: str,
     per-file row counts recovered with a searchsorted over frame offsets.
     Uncompressed files DMA straight from the page cache; gzip files bearing
     our segment table are inflated by the device inflater (all files'
-    segments in one launch). With `foreign_gzip`, gzip files without the
+    segments in one launch); `.snappy` files are decoded by the device
+    Snappy decoder (all files' chunks in one launch), and SnappyRejected
+    names those it refuses. With `foreign_gzip`, gzip files without the
     table go through the speculative inflater into their own slices of the
     same image; if it refuses any, ForeignGzipRejected names them and
     nothing is decoded. Returns (device RecordBatch, np.ndarray row_counts
@@ -1592,8 +1761,20 @@ def read_files_to_batch(paths, schema: StructType, record_type: str,
     check_native()
     metas = []
     fmetas = []
+    smetas = []
     sizes = []
     for p in paths:
+        if P.codec_from_path(p) == "snappy":
+            smeta = snappy_device_meta(p)
+            if smeta is None:
+                raise ValueError(f"snappy file not for the device decoder: "
+                                 f"{p} (host path required)")
+            metas.append(None)
+            fmetas.append(None)
+            smetas.append(smeta)
+            sizes.append(smeta[1])
+            continue
+        smetas.append(None)
         if P.codec_from_path(p) == "gzip":
             meta = P.parse_gz_segments_file(p)
             fmeta = None
@@ -1626,8 +1807,12 @@ def read_files_to_batch(paths, schema: StructType, record_type: str,
     streams = _dma_streams()
     gz_items = []
     foreign_items = []
+    snappy_items = []
     for i, p in enumerate(paths):
         if not sizes[i]:
+            continue
+        if smetas[i] is not None:
+            snappy_items.append((p, smetas[i], int(bounds[i])))
             continue
         if metas[i] is not None:
             gz_items.append((p, metas[i], int(bounds[i])))
@@ -1650,6 +1835,13 @@ def read_files_to_batch(paths, schema: StructType, record_type: str,
             # a refused file's true length is unknown (its ISIZE may be
             # another member's), so the image layout cannot be kept
             raise ForeignGzipRejected(refused)
+    if snappy_items:
+        ok = _device_unsnap_group(data, snappy_items, device)
+        refused = [it[0] for it, good in zip(snappy_items, ok) if not good]
+        if refused:
+            # the host decoder decides what a refused file is: its bytes,
+            # or an error that names the file
+            raise SnappyRejected(refused)
     if gz_items and not _device_inflate_group(data, gz_items, device):
         # rare fallback: a segment the kernel rejected — host zlib fills
         # the affected files' slices

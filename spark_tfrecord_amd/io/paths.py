@@ -35,12 +35,14 @@ _CODEC_ALIASES = {
     "deflate": "deflate",
     "org.apache.hadoop.io.compress.deflatecodec": "deflate",
     "org.apache.hadoop.io.compress.defaultcodec": "deflate",
+    "snappy": "snappy",
+    "org.apache.hadoop.io.compress.snappycodec": "snappy",
     "none": None,
     "uncompressed": None,
 }
 
-_EXTENSIONS = {"gzip": ".gz", "deflate": ".deflate"}
-_EXT_TO_CODEC = {".gz": "gzip", ".deflate": "deflate"}
+_EXTENSIONS = {"gzip": ".gz", "deflate": ".deflate", "snappy": ".snappy"}
+_EXT_TO_CODEC = {".gz": "gzip", ".deflate": "deflate", ".snappy": "snappy"}
 
 
 class SaveModeError(RuntimeError):
@@ -161,7 +163,150 @@ def compress_bytes(data: bytes, codec: Optional[str]) -> bytes:
         return hdr + b"".join(chunks) + trailer
     if codec == "deflate":
         return zlib.compress(data, 6)
+    if codec == "snappy":
+        return snappy_compress(data)
     raise ValueError(codec)
+
+
+# ---------------------------------------------------------------------------
+# Snappy: Hadoop block container around raw Snappy chunks
+# ---------------------------------------------------------------------------
+
+# Uncompressed bytes per block the writer emits. 64 KiB is Snappy's own
+# fragment size (the library never matches across it), so smaller blocks
+# than Hadoop's 256 KiB default cost no ratio, and every block is one unit
+# of parallel work for the readers.
+_SNAPPY_BLOCK = int(os.environ.get("TFREC_SNAPPY_BLOCK", 64 << 10))
+
+
+def snappy_block_size() -> int:
+    if _SNAPPY_BLOCK <= 0 or _SNAPPY_BLOCK >= (1 << 32):
+        raise ValueError(
+            f"TFREC_SNAPPY_BLOCK must be in 1..2^32-1, got {_SNAPPY_BLOCK}")
+    return _SNAPPY_BLOCK
+
+
+def _snappy_raw():
+    import pyarrow as pa
+
+    return pa.Codec("snappy")
+
+
+def snappy_pack_block(raw, codec=None) -> bytes:
+    """One container block holding `raw` (non-empty) as a single chunk."""
+    import struct as _struct
+
+    comp = (codec or _snappy_raw()).compress(raw, asbytes=True)
+    return _struct.pack(">II", len(raw), len(comp)) + comp
+
+
+def snappy_compress(data) -> bytes:
+    """Hadoop block container (layout: snappy_walk) of `data`, one chunk
+    per block of at most TFREC_SNAPPY_BLOCK raw bytes. Compresses block by
+    block in the calling thread: this runs on shared_pool() workers, and
+    waiting on that pool from inside it can deadlock."""
+    block = snappy_block_size()
+    codec = _snappy_raw()
+    view = memoryview(data)
+    return b"".join(snappy_pack_block(view[pos:pos + block], codec)
+                    for pos in range(0, len(view), block))
+
+
+def _snappy_preamble(buf, pos: int, end: int) -> Optional[int]:
+    """The varint uncompressed length leading a raw Snappy chunk at
+    buf[pos:end], or None when it does not terminate within 5 bytes."""
+    val = 0
+    for k in range(min(5, end - pos)):
+        b = buf[pos + k]
+        val |= (b & 0x7F) << (7 * k)
+        if not b & 0x80:
+            return val
+    return None
+
+
+def snappy_walk(buf, name: str):
+    """Walk the Hadoop block container of a `.snappy` file image.
+
+    THE LAYOUT (BlockCompressorStream / BlockDecompressorStream, written
+    from their description; not yet checked against a file that Hadoop or
+    TensorFlow wrote, see docs/PARITY.md): the file is a sequence of
+    blocks. A block is
+        u32 big-endian raw_len      uncompressed bytes the block holds
+    followed by one or more chunks, each
+        u32 big-endian comp_len     bytes of raw Snappy that follow
+        comp_len bytes              raw Snappy: a varint of the chunk's own
+                                    uncompressed length, then elements
+    and the chunks go on until their uncompressed lengths add up to
+    raw_len. A block with raw_len 0 ends the stream (Hadoop's reader stops
+    there); so does the end of the file. An empty stream is a zero-byte
+    file. Our writer puts one chunk in every block and never writes
+    raw_len 0; the reader takes any block and chunk sizes.
+
+    `buf` is bytes-like (bytes, memoryview, mmap). Returns
+    ([(in_off, in_len, out_off, out_len), ...], total_raw): each chunk's
+    extent in `buf` and in the uncompressed image. Raises ValueError naming
+    `name` and the block for a truncated header, a comp_len that runs past
+    the end, or a chunk whose preamble disagrees with what its block has
+    left. The chunks' elements are not looked at."""
+    import struct as _struct
+
+    n = len(buf)
+    pos = 0
+    out_off = 0
+    block = 0
+    chunks = []
+    while pos < n:
+        if pos + 4 > n:
+            raise ValueError(f"{name}: snappy block {block}: truncated "
+                             f"block header at byte {pos}")
+        (raw_len,) = _struct.unpack_from(">I", buf, pos)
+        pos += 4
+        if raw_len == 0:
+            break
+        left = raw_len
+        while left > 0:
+            if pos + 4 > n:
+                raise ValueError(f"{name}: snappy block {block}: truncated "
+                                 f"chunk header at byte {pos}")
+            (comp_len,) = _struct.unpack_from(">I", buf, pos)
+            pos += 4
+            if comp_len > n - pos:
+                raise ValueError(
+                    f"{name}: snappy block {block}: chunk of {comp_len} "
+                    f"bytes at byte {pos} runs past the end of the file")
+            want = _snappy_preamble(buf, pos, pos + comp_len)
+            if want is None or want == 0 or want > left:
+                raise ValueError(
+                    f"{name}: snappy block {block}: chunk at byte {pos} "
+                    f"declares {want} bytes, the block has {left} left")
+            chunks.append((pos, comp_len, out_off, want))
+            pos += comp_len
+            out_off += want
+            left -= want
+        block += 1
+    return chunks, out_off
+
+
+def snappy_decompress(buf, name: str) -> bytes:
+    """Uncompressed image of a `.snappy` file image (layout: snappy_walk),
+    chunk by chunk through the library in the calling thread."""
+    chunks, total = snappy_walk(buf, name)
+    if not chunks:
+        return b""
+    codec = _snappy_raw()
+    view = memoryview(buf)
+    parts = []
+    for k, (io, il, _oo, ol) in enumerate(chunks):
+        try:
+            parts.append(codec.decompress(view[io:io + il],
+                                          decompressed_size=ol, asbytes=True))
+        except Exception as e:  # noqa: BLE001 - the library's own error type
+            raise ValueError(f"{name}: snappy chunk {k} at byte {io} is "
+                             f"corrupt: {e}") from None
+        if len(parts[-1]) != ol:
+            raise ValueError(f"{name}: snappy chunk {k} at byte {io} is "
+                             f"corrupt: {len(parts[-1])} bytes, not {ol}")
+    return b"".join(parts)
 
 
 def parse_gz_segments(raw: bytes):
@@ -302,6 +447,8 @@ def decompress_file(path: str) -> bytes:
         return out if out is not None else gzip.decompress(raw)
     if codec == "deflate":
         return zlib.decompress(raw)
+    if codec == "snappy":
+        return snappy_decompress(raw, path)
     raise ValueError(codec)
 
 

@@ -68,16 +68,19 @@ def infer_schema_of_paths(files: List[str], record_type: str,
     if record_type == "ByteArray":
         return byte_array_schema()
     for f in files:
-        if engine == "gpu" and P.codec_from_path(f) in (None, "gzip"):
+        if engine == "gpu" and P.codec_from_path(f) in (None, "gzip",
+                                                        "snappy"):
             import os as _os
 
             if _os.path.getsize(f) == 0:
                 continue
             from ..engine import gpu as gpu_engine
 
-            if P.codec_from_path(f) == "gzip":
-                data = gpu_engine.read_gzip_file_to_device(f)
-                if data is None:  # foreign gzip: host inflate + lattice
+            if P.codec_from_path(f) in ("gzip", "snappy"):
+                data = (gpu_engine.read_gzip_file_to_device(f)
+                        if P.codec_from_path(f) == "gzip"
+                        else gpu_engine.read_snappy_file_to_device(f))
+                if data is None:  # not for the device: host bytes + lattice
                     data_np = _load_file(f)
                     if data_np.size == 0:
                         continue
@@ -140,14 +143,16 @@ def count_tfrecord(path: str, engine: str = "auto") -> int:
     eng = engine_mod.resolve_engine(engine)
     total = 0
     for f in files:
-        if eng == "gpu" and P.codec_from_path(f) in (None, "gzip"):
+        if eng == "gpu" and P.codec_from_path(f) in (None, "gzip", "snappy"):
             if os.path.getsize(f) == 0:
                 continue
             from ..engine import gpu as gpu_engine
 
-            if P.codec_from_path(f) == "gzip":
-                data = gpu_engine.read_gzip_file_to_device(f)
-                if data is None:  # foreign gzip: host count below
+            if P.codec_from_path(f) in ("gzip", "snappy"):
+                data = (gpu_engine.read_gzip_file_to_device(f)
+                        if P.codec_from_path(f) == "gzip"
+                        else gpu_engine.read_snappy_file_to_device(f))
+                if data is None:  # foreign gzip / refused snappy: host count
                     data_np = _load_file(f)
                     if data_np.size:
                         off_h, _ = _native.scan_frames(data_np, False)
@@ -199,7 +204,7 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
     part_cols = _partition_schema(files, base_dir) if base_dir else []
     eng = engine_mod.resolve_engine(engine)
     foreign_device = _resolve_foreign_gzip(foreign_gzip, eng)
-    host_only: set = set()  # foreign gzip files the device refused
+    host_only: set = set()  # compressed files the device refused
 
     metrics = IOMetrics("read")
 
@@ -235,6 +240,12 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
             # for and the file is eligible
             return not (foreign_device
                         and gpu_engine.foreign_gz_meta(fpath) is not None)
+        if codec == "snappy":
+            # the block headers give every chunk's extents: the device
+            # decoder takes the file unless the walk fails, a chunk is over
+            # its cap, or TFREC_SNAPPY=host
+            from ..engine import gpu as gpu_engine
+            return gpu_engine.snappy_device_meta(fpath) is None
         return True
 
     # Schema-less GPU reads DEFER inference into the first group pipeline:
@@ -348,15 +359,21 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
                         batch, row_counts = gpu_engine.read_files_to_batch(
                             group, data_schema, record_type,
                             verify_crc=verify_crc, foreign_gzip=foreign_device)
-                except gpu_engine.ForeignGzipRejected as rej:
+                except gpu_engine.DeviceDecompressRejected as rej:
                     # redo the group without the refused files: they take
-                    # the host path, as with foreign_gzip="host"
+                    # the host path, as with foreign_gzip="host" (gzip) or
+                    # TFREC_SNAPPY=host (snappy)
                     import logging
 
                     for p in rej.paths:
-                        logging.getLogger(__name__).warning(
-                            "device inflate refused foreign gzip file %s; "
-                            "host zlib fallback", p)
+                        if isinstance(rej, gpu_engine.ForeignGzipRejected):
+                            logging.getLogger(__name__).warning(
+                                "device inflate refused foreign gzip file "
+                                "%s; host zlib fallback", p)
+                        else:
+                            logging.getLogger(__name__).warning(
+                                "device decode refused %s; host codec "
+                                "fallback", p)
                     host_only.update(rej.paths)
                     i = i0
                     continue

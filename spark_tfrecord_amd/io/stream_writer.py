@@ -15,6 +15,10 @@ outgrows the reserved table (`segment_table_capacity`), the table is
 dropped (padding only) and reads fall back to the full-flush marker scan,
 exactly like a foreign gzip file.
 
+snappy shards buffer raw bytes up to one container block (io/paths.py
+snappy_walk), emit each full block as it fills and the short tail on
+close: the file is the one `write_tfrecord` writes for the same bytes.
+
     with ShardWriter(path + "/part-00000.tfrecord", schema) as w:
         for chunk in produce():
             w.write(chunk)
@@ -53,6 +57,7 @@ class ShardWriter:
         self._f = open(self._tmp, "wb")
         self._gz = None
         self._zl = None
+        self._sn_buf = None
         if self.codec == "gzip":
             # raw-deflate stream + hand-rolled gzip framing so the header
             # can reserve the FEXTRA segment-table region (backpatched on
@@ -72,6 +77,11 @@ class ShardWriter:
             self._seg_comp = 0  # compressed bytes already written for it
         elif self.codec == "deflate":
             self._zl = zlib.compressobj(6)
+        elif self.codec == "snappy":
+            # raw bytes wait here until they fill a container block
+            self._sn_buf = bytearray()
+            self._sn_block = P.snappy_block_size()
+            self._sn_codec = P._snappy_raw()
         self._closed = False
 
     # -- context manager --------------------------------------------------
@@ -133,6 +143,21 @@ class ShardWriter:
         self._f.write(extra)
         self._f.seek(0, os.SEEK_END)
 
+    # -- snappy block stream ------------------------------------------------
+    def _sn_append(self, raw: bytes, final: bool = False):
+        """Buffer `raw`, emit every full block (the same blocks
+        `compress_bytes` cuts), and the short tail when `final`."""
+        self._sn_buf += raw
+        block = self._sn_block
+        view = memoryview(self._sn_buf)
+        pos = 0
+        while len(view) - pos >= block or (final and pos < len(view)):
+            self._f.write(P.snappy_pack_block(view[pos:pos + block],
+                                              self._sn_codec))
+            pos += block
+        view.release()
+        del self._sn_buf[:pos]
+
     # -- writing -----------------------------------------------------------
     def write(self, data) -> int:
         """Append a chunk of rows; returns rows written so far."""
@@ -157,6 +182,8 @@ class ShardWriter:
         elif self._zl is not None:
             self._f.write(self._zl.compress(raw))
             self._f.write(self._zl.flush(zlib.Z_FULL_FLUSH))
+        elif self._sn_buf is not None:
+            self._sn_append(raw)
         else:
             self._f.write(raw)
         self.rows_written += table.num_rows
@@ -170,6 +197,8 @@ class ShardWriter:
             self._gz_finish()
         elif self._zl is not None:
             self._f.write(self._zl.flush())
+        elif self._sn_buf is not None:
+            self._sn_append(b"", final=True)
         self._f.flush()
         os.fsync(self._f.fileno())
         self._f.close()
