@@ -21,6 +21,11 @@ driver runs it). This suite covers the rest, each printing one JSON line:
                   "device"), as one file and as 32 files
   gzip_bytearray  config 5: gzip-compressed ByteArray read, shard staged
                   through HBM on the GPU engine
+  collate         dense training batches of 8192 flagship rows from 8
+                  shards: TFRecordIterableDataset (ragged wire form) against
+                  TFRecordBatchDataset (collate kernel) without and with a
+                  shuffle window, and the kernel against the same collation
+                  in torch indexing ops on one decoded shard
 
 Single process:  python bench_suite.py all --rows 100000
 Multi GPU:       torchrun --nproc-per-node 8 bench_suite.py partitionby
@@ -485,11 +490,187 @@ def bench_snappy(args):
     shutil.rmtree(d, ignore_errors=True)
 
 
+def _torch_collate(batch, lo, hi, torch):
+    """The flagship spec (id FixedLen(), ints Padded(8), floats FixedLen(16),
+    tokens Padded2D(2, 12)) for rows [lo, hi) of one decoded shard in torch
+    indexing ops only, with no host wait: the comparison for
+    collate_rows_kernel. General in the counts (it reads the offsets), as the
+    kernel is; the error flag stays on the device."""
+    idc, ints, floats, tokens = (batch.column(n) for n in
+                                 ("id", "ints", "floats", "tokens"))
+    dev = idc.values.device
+
+    def padded(col, L, pad):
+        start = col.row_off[lo:hi]
+        cnt = col.row_off[lo + 1:hi + 1] - start
+        j = torch.arange(L, device=dev)
+        idx = (start[:, None] + j).clamp_(max=col.values.numel() - 1)
+        v = torch.where(j < cnt[:, None], col.values[idx], pad)
+        return v, cnt
+
+    out = {}
+    v, cnt = padded(idc, 1, 0)
+    out["id"] = v[:, 0]
+    bad = (cnt != 1).any()
+    out["ints"], cnt = padded(ints, 8, 0)
+    out["ints_len"] = cnt.clamp(max=8).int()
+    bad = bad | (cnt > 8).any()
+    out["floats"], cnt = padded(floats, 16, 0.0)
+    bad = bad | (cnt != 16).any()
+    T, L = 2, 12
+    start = tokens.row_off[lo:hi]
+    oc = tokens.row_off[lo + 1:hi + 1] - start
+    t = torch.arange(T, device=dev)
+    item = (start[:, None] + t).clamp_(max=tokens.elem_off.numel() - 2)
+    b0 = tokens.elem_off[item]
+    ln = torch.where(t < oc[:, None], tokens.elem_off[item + 1] - b0, 0)
+    j = torch.arange(L, device=dev)
+    idx = (b0[..., None] + j).clamp_(max=tokens.values.numel() - 1)
+    out["tokens"] = torch.where(j < ln[..., None], tokens.values[idx], 0)
+    out["tokens_outer"] = oc.clamp(max=T).int()
+    out["tokens_len"] = ln.clamp(max=L).int()
+    out["_bad"] = bad | (oc > T).any() | (ln > L).any()
+    return out
+
+
+def bench_collate(args):
+    """--rows flagship Example rows in 8 shards, batches of 8192. Whole
+    pipelines, alternating after a warm-up of each: (a) the ragged
+    TFRecordIterableDataset, (b) TFRecordBatchDataset with shuffle_window=0,
+    (c) the same with shuffle_window=4, (c4) that with prefetch=4. Collation
+    alone over one decoded
+    shard: (k) collate_rows_kernel through Collator.run, (d) the same four
+    columns in torch indexing ops. --collate-part kernel|torch runs only
+    (k) or (d), for a kernel trace of its own; none only decodes the shard."""
+    import torch
+
+    import spark_tfrecord_amd as stf
+    from spark_tfrecord_amd.collate import Collator
+    from spark_tfrecord_amd.engine import gpu as gpu_engine
+    from spark_tfrecord_amd.io import paths as P
+    from spark_tfrecord_amd.torch_data import (FixedLen, Padded, Padded2D,
+                                               TFRecordBatchDataset,
+                                               TFRecordIterableDataset)
+
+    rank, world = _env_world()
+    if not torch.cuda.is_available():
+        raise SystemExit("collate needs the GPU engine")
+    rows, B = args.rows, 8192
+    d = _workdir("collate", rank)
+    out = os.path.join(d, "t")
+    stf.write_tfrecord(_flagship_table(rows, 9 + rank), out,
+                       record_type="Example", num_shards=8, engine="gpu")
+    schema = stf.read_tfrecord(out, engine="gpu").schema
+    spec = {"id": FixedLen(), "ints": Padded(8), "floats": FixedLen(16),
+            "tokens": Padded2D(2, 12)}
+    part = args.collate_part
+
+    # -- collation alone, one decoded shard --------------------------------
+    shard = gpu_engine.read_file_to_batch(P.list_data_files(out)[0], schema,
+                                          "Example", True)
+    R = shard.num_rows
+    ranges = [(lo, min(R, lo + B)) for lo in range(0, R, B)]
+    co = Collator(schema, spec, "gpu")
+    co.set_window([shard])
+    sels = [(np.zeros(hi - lo, np.int32), np.arange(lo, hi, dtype=np.int64))
+            for lo, hi in ranges]
+
+    def run_kernel():
+        for slot, row in sels:
+            outs, status = co.run(slot, row)
+        assert status[0] == (1 << 64) - 1
+        return outs
+
+    def run_torch():
+        for lo, hi in ranges:
+            outs = _torch_collate(shard, lo, hi, torch)
+        assert not bool(outs["_bad"])  # the one wait, as the kernel's
+        return outs
+
+    alone = {"kernel": run_kernel, "torch": run_torch}
+    if part in ("kernel", "torch", "none"):
+        alone = {k: f for k, f in alone.items() if k == part}
+    if part == "all":
+        a, b = run_kernel(), run_torch()
+        for k in a:  # the two collations agree
+            assert torch.equal(a[k], b[k]), k
+    el_alone = dict.fromkeys(alone, 0.0)
+    for f in alone.values():
+        f()  # warm-up
+    torch.cuda.synchronize()
+    for _ in range(args.reps):
+        for k, f in alone.items():
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            el_alone[k] += time.perf_counter() - t0
+    for k, t in el_alone.items():
+        _emit(rank, f"rows/sec collate alone ({k}), one shard", R * args.reps / t,
+              "rows/s", {"rows": R, "batch": B, "batches": len(ranges),
+                         "reps": args.reps, "part": k,
+                         "ms_per_batch": round(
+                             t * 1e3 / (args.reps * len(ranges)), 4),
+                         "engine": "gpu"}, t, 1)
+    if part != "all":
+        shutil.rmtree(d, ignore_errors=True)
+        return
+
+    # -- whole pipelines ---------------------------------------------------
+    def ragged():
+        n = 0
+        for b in TFRecordIterableDataset(out, schema=schema, batch_rows=B,
+                                         engine="gpu"):
+            n += b["id"].numel()
+        return n
+
+    stats = {}
+
+    def dense(window, prefetch=1):
+        def run():
+            ds = TFRecordBatchDataset(out, spec, batch_size=B,
+                                      shuffle_window=window, engine="gpu",
+                                      schema=schema, prefetch=prefetch)
+            n = 0
+            for b in ds:
+                n += b["id"].shape[0]
+            stats[window] = dict(ds.last_stats)
+            return n
+        return run
+
+    # the slots of a window drain at about the same time, so (c) refills in
+    # bursts of 4 decodes; the last mode lets the decode thread run 4 ahead
+    # (measured: no gain, profiles/RESULTS.md "Batch collation")
+    modes = {"a: TFRecordIterableDataset (ragged)": ragged,
+             "b: TFRecordBatchDataset shuffle_window=0": dense(0),
+             "c: TFRecordBatchDataset shuffle_window=4": dense(4),
+             "c4: TFRecordBatchDataset shuffle_window=4 prefetch=4":
+                 dense(4, 4)}
+    el = dict.fromkeys(modes, 0.0)
+    for f in modes.values():
+        assert f() == rows  # warm-up
+    torch.cuda.synchronize()
+    for _ in range(args.reps):
+        for m, f in modes.items():
+            t0 = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            el[m] += time.perf_counter() - t0
+    ta = el["a: TFRecordIterableDataset (ragged)"]
+    for m, t in el.items():
+        w = None if m.startswith("a") else 0 if m.startswith("b") else 4
+        _emit(rank, f"rows/sec training batches, {m}", rows * args.reps / t,
+              "rows/s", {"rows": rows, "files": 8, "batch": B,
+                         "over_ragged": round(ta / t, 3),
+                         "last_stats": stats.get(w), "engine": "gpu",
+                         "reps": args.reps}, t, 1)
+    shutil.rmtree(d, ignore_errors=True)
+
+
 BENCHES = {"plumbing": bench_plumbing, "partitionby": bench_partitionby,
            "infer": bench_infer, "gzip_bytearray": bench_gzip_bytearray,
            "gzip_write": bench_gzip_write,
            "gzip_foreign": bench_gzip_foreign,
-           "snappy": bench_snappy}
+           "snappy": bench_snappy, "collate": bench_collate}
 
 
 def main():
@@ -497,6 +678,10 @@ def main():
     ap.add_argument("which", choices=list(BENCHES) + ["all"])
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--collate-part", default="all",
+                    choices=["all", "kernel", "torch", "none"],
+                    help="collate: run only one collation-alone loop "
+                         "(for a kernel trace of its own)")
     args = ap.parse_args()
     names = list(BENCHES) if args.which == "all" else [args.which]
     for n in names:

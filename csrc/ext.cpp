@@ -33,6 +33,7 @@
 #include "inflate_core.h"
 #include "inflate_spec_core.h"
 #include "snappy_core.h"
+#include "collate_core.h"
 
 namespace py = pybind11;
 using namespace tfrec;
@@ -830,6 +831,34 @@ py::bytes host_unsnap_chunk(py::buffer comp, i64 expect_len) {
   return py::bytes(out);
 }
 
+// Host run of the batch collation core shared with the gfx950 kernel
+// (csrc/collate_core.h): the same do_unit over every unit of every column,
+// in plain loops. The tables hold host addresses of numpy buffers the caller
+// keeps alive; geometry is checked by the caller (collate.py), as for the
+// kernel. This is the CPU engine's collation, not only a test hook.
+void host_collate(py::array_t<i64, py::array::c_style> src,
+                  py::array_t<i64, py::array::c_style> cols,
+                  py::array_t<int32_t, py::array::c_style> sel_slot,
+                  py::array_t<i64, py::array::c_style> sel_row,
+                  py::array_t<u64, py::array::c_style> status) {
+  namespace cl = tfrec::collate;
+  static_assert(sizeof(cl::Src) == cl::kSrcWords * 8, "Src layout");
+  static_assert(sizeof(cl::Col) == cl::kColWords * 8, "Col layout");
+  const i64 ncols = cols.size() / cl::kColWords;
+  const i64 B = sel_slot.size();
+  if (ncols <= 0 || ncols > cl::kMaxCols || cols.size() % cl::kColWords)
+    throw std::invalid_argument("host_collate: 1..64 columns of 12 words");
+  if (sel_row.size() != B || status.size() != 2 ||
+      src.size() % (ncols * cl::kSrcWords))
+    throw std::invalid_argument("host_collate: table sizes disagree");
+  cl::Batch bt{reinterpret_cast<const cl::Src*>(src.data()),
+               reinterpret_cast<const cl::Col*>(cols.data()),
+               sel_slot.data(), sel_row.data(), ncols, B,
+               status.mutable_data()};
+  py::gil_scoped_release nogil;
+  cl::host_run(bt);
+}
+
 std::vector<int> host_huffman_lengths(const std::vector<u32>& freqs,
                                       int max_len) {
   if (freqs.size() > 288 || max_len < 1 || max_len > 15)
@@ -869,6 +898,7 @@ void register_inflate(py::module_& m);  // defined in csrc/hip/inflate.hip
 void register_deflate(py::module_& m);  // defined in csrc/hip/deflate.hip
 void register_inflate_foreign(py::module_& m);  // csrc/hip/inflate_foreign.hip
 void register_snappy(py::module_& m);   // defined in csrc/hip/snappy.hip
+void register_collate(py::module_& m);  // defined in csrc/hip/collate.hip
 
 PYBIND11_MODULE(_native, m) {
   m.doc() = "MI355X-native TFRecord codec (host + gfx950 kernels)";
@@ -901,6 +931,14 @@ PYBIND11_MODULE(_native, m) {
         py::arg("expect_len"),
         "TEST-ONLY: run the device Snappy decoder's core on host for one raw "
         "chunk; raises RuntimeError naming the cause code on a refusal");
+  m.def("host_collate", &host_collate, py::arg("src"), py::arg("cols"),
+        py::arg("sel_slot"), py::arg("sel_row"), py::arg("status"),
+        "Collate (slot, row) pairs into the dense outputs of the column "
+        "table on the host (the kernel's core in plain loops)");
+  m.attr("COLLATE_SRC_WORDS") = (int)tfrec::collate::kSrcWords;
+  m.attr("COLLATE_COL_WORDS") = (int)tfrec::collate::kColWords;
+  m.attr("COLLATE_TILE_UNITS") = (int)tfrec::collate::kTileUnits;
+  m.attr("COLLATE_MAX_COLS") = (int)tfrec::collate::kMaxCols;
   m.def("host_huffman_lengths", &host_huffman_lengths, py::arg("freqs"),
         py::arg("max_len"),
         "TEST-ONLY: length-limited Huffman code lengths of the compressor core");
@@ -932,6 +970,7 @@ PYBIND11_MODULE(_native, m) {
   register_deflate(m);
   register_inflate_foreign(m);
   register_snappy(m);
+  register_collate(m);
   m.attr("HAS_GPU_KERNELS") = true;
 #else
   m.attr("HAS_GPU_KERNELS") = false;

@@ -10,12 +10,22 @@ torch.distributed ranks and DataLoader workers round-robin.
     ds = TFRecordIterableDataset(path, batch_rows=8192)
     for batch in ds:           # dict: name -> values tensor,
         ...                    #       name+"_offsets" -> row offsets (ragged)
+
+TFRecordBatchDataset goes the rest of the way: dense, shuffled batches of a
+fixed size, collated on the device from a window of decoded shards
+(collate.py; one kernel launch and one host wait per batch).
+
+    ds = TFRecordBatchDataset(path, features={"id": FixedLen(),
+                                              "ints": Padded(8)},
+                              batch_size=8192, shuffle_window=4)
+    for batch in ds:           # dict: name -> [B], [B, L] or [B, T, L]
+        ...
 """
 
 from __future__ import annotations
 
 import os
-from typing import Dict, Iterator, List, Optional, Sequence
+from typing import Any, Dict, Iterator, List, Optional, Sequence
 
 import numpy as np
 import torch
@@ -25,8 +35,11 @@ from .infer import byte_array_schema
 from .io import paths as P
 from .schema import KIND_BYTES, StructType
 from .columnar import RecordBatch
+from .collate import (STATUS_CLEAN, Collator, FixedLen, Padded, Padded2D,
+                      plan_columns)
 
-__all__ = ["TFRecordIterableDataset"]
+__all__ = ["TFRecordIterableDataset", "TFRecordBatchDataset", "FixedLen",
+           "Padded", "Padded2D"]
 
 
 def _as_torch(x, device):
@@ -64,34 +77,20 @@ def _slice_col(col, lo: int, hi: int, device):
     return out
 
 
-class TFRecordIterableDataset(torch.utils.data.IterableDataset):
-    """Iterates dicts of tensors over a TFRecord dataset.
+class _ShardSource(torch.utils.data.IterableDataset):
+    """What both datasets share: the file list and schema, the assignment of
+    shards to ranks and workers, the per-shard decode dispatch and the
+    prefetch thread."""
 
-    Each yielded item covers up to `batch_rows` rows of one shard:
-      {col: values, col+"_offsets": per-row value offsets,
-       col+"_presence": u8 mask, and for string/seq columns also
-       col+"_value_offsets" / col+"_list_offsets" / col+"_sub_offsets"}.
+    shuffle_files = False
+    seed = 0
 
-    `device` "cuda": files decode on the GPU and tensors stay device-resident.
-    Files are sharded across dist ranks (rank r takes files r, r+W, ...)
-    and then across DataLoader workers the same way.
-    """
-
-    def __init__(self, path: str, schema: Optional[StructType] = None,
-                 record_type: str = "Example", batch_rows: int = 65536,
-                 columns: Optional[Sequence[str]] = None,
-                 engine: str = "auto", verify_crc: bool = True,
-                 shuffle_files: bool = False, seed: int = 0,
-                 prefetch: int = 1, foreign_gzip: Optional[str] = None):
-        super().__init__()
+    def _init_source(self, path, schema, record_type, engine, verify_crc,
+                     prefetch, foreign_gzip):
         self.path = path
         self.record_type = record_type
-        self.batch_rows = int(batch_rows)
-        self.columns = list(columns) if columns else None
         self.engine = engine
         self.verify_crc = verify_crc
-        self.shuffle_files = shuffle_files
-        self.seed = seed
         self.prefetch = int(prefetch)  # shards decoded ahead (0 = sync)
         # "device": other writers' gzip shards inflate on the GPU too
         # (read_tfrecord's option of the same name); checked here, resolved
@@ -175,19 +174,17 @@ class TFRecordIterableDataset(torch.utils.data.IterableDataset):
         return cpu_engine.decode_buffer(data, sub_schema, self.record_type,
                                         self.verify_crc)
 
-    def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
-        eng = engine_mod.resolve_engine(self.engine)
+    def _decoded_shards(self, eng: str, sub_schema):
+        """Yields (path, RecordBatch) for this rank's and worker's non-empty
+        shards, in order, decoded `prefetch` shards ahead."""
         from .io.reader import _resolve_foreign_gzip
         self._foreign_device = _resolve_foreign_gzip(self.foreign_gzip, eng)
-        fields = [f for f in self.schema.fields
-                  if self.columns is None or f.name in self.columns]
-        sub_schema = StructType(fields)
         files = self._my_files()
         if self.prefetch <= 0:
             for fpath in files:
                 batch = self._decode_one(fpath, eng, sub_schema)
                 if batch is not None:
-                    yield from self._emit(batch, fields, None)
+                    yield fpath, batch
             return
         # background prefetch: a worker thread decodes the next shard(s) on
         # its own CUDA stream while the consumer drains the current one
@@ -208,7 +205,7 @@ class TFRecordIterableDataset(torch.utils.data.IterableDataset):
                     else:
                         b = self._decode_one(fpath, eng, sub_schema)
                     if b is not None:
-                        q.put(b)
+                        q.put((fpath, b))
                 q.put(SENTINEL)
             except BaseException as e:  # noqa: BLE001 — surface in consumer
                 q.put(e)
@@ -221,7 +218,43 @@ class TFRecordIterableDataset(torch.utils.data.IterableDataset):
                 break
             if isinstance(item, BaseException):
                 raise item
-            yield from self._emit(item, fields, None)
+            yield item
+
+
+class TFRecordIterableDataset(_ShardSource):
+    """Iterates dicts of tensors over a TFRecord dataset.
+
+    Each yielded item covers up to `batch_rows` rows of one shard:
+      {col: values, col+"_offsets": per-row value offsets,
+       col+"_presence": u8 mask, and for string/seq columns also
+       col+"_value_offsets" / col+"_list_offsets" / col+"_sub_offsets"}.
+
+    `device` "cuda": files decode on the GPU and tensors stay device-resident.
+    Files are sharded across dist ranks (rank r takes files r, r+W, ...)
+    and then across DataLoader workers the same way.
+    """
+
+    def __init__(self, path: str, schema: Optional[StructType] = None,
+                 record_type: str = "Example", batch_rows: int = 65536,
+                 columns: Optional[Sequence[str]] = None,
+                 engine: str = "auto", verify_crc: bool = True,
+                 shuffle_files: bool = False, seed: int = 0,
+                 prefetch: int = 1, foreign_gzip: Optional[str] = None):
+        super().__init__()
+        self.batch_rows = int(batch_rows)
+        self.columns = list(columns) if columns else None
+        self.shuffle_files = shuffle_files
+        self.seed = seed
+        self._init_source(path, schema, record_type, engine, verify_crc,
+                          prefetch, foreign_gzip)
+
+    def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
+        eng = engine_mod.resolve_engine(self.engine)
+        fields = [f for f in self.schema.fields
+                  if self.columns is None or f.name in self.columns]
+        sub_schema = StructType(fields)
+        for _, batch in self._decoded_shards(eng, sub_schema):
+            yield from self._emit(batch, fields, None)
 
     def _emit(self, batch: RecordBatch, fields, device):
         R = batch.num_rows
@@ -238,3 +271,185 @@ class TFRecordIterableDataset(torch.utils.data.IterableDataset):
                         out[f"{f.name}_{k}"] = parts[k]
             out["_num_rows"] = torch.tensor(hi - lo)
             yield out
+
+
+class _Slot:
+    """One decoded shard in the shuffle window."""
+
+    __slots__ = ("path", "batch", "perm", "cursor", "retired")
+
+    def __init__(self, path, batch, perm):
+        self.path, self.batch, self.perm = path, batch, perm
+        self.cursor = 0
+        self.retired = False
+
+    @property
+    def left(self) -> int:
+        return self.batch.num_rows - self.cursor
+
+
+class TFRecordBatchDataset(_ShardSource):
+    """Dense batches of exactly `batch_size` rows, shuffled through a window
+    of decoded shards and collated per `features` (name -> FixedLen / Padded
+    / Padded2D, see collate.py).
+
+    The window holds up to `shuffle_window` decoded shards; each has a
+    seeded permutation of its rows. A batch draws `batch_size` rows
+    uniformly without replacement from all rows left in the window, and a
+    drained shard is replaced by the next one before the next draw.
+    `shuffle_window=0`: no shuffle, rows in file order, batches crossing
+    shard boundaries. The sampler is host-side numpy seeded from (seed,
+    epoch, rank, worker) and sees only the shards' row counts, so both
+    engines yield the same batches in the same order. Shards are visited in
+    listing order; only the spec'd columns are decoded.
+
+    engine "gpu": shards decode on the device and stay there; per batch only
+    the selection crosses the link, one kernel gathers every column, and the
+    iterator waits once, on the status words. `truncated_rows` accumulates
+    over an iteration; `last_stats` holds the last iteration's batches,
+    kernel launches and host waits.
+    """
+
+    def __init__(self, path: str, features: Dict[str, Any],
+                 batch_size: int = 8192, shuffle_window: int = 4,
+                 seed: int = 0, drop_last: bool = False,
+                 engine: str = "auto", schema: Optional[StructType] = None,
+                 record_type: str = "Example", verify_crc: bool = True,
+                 prefetch: int = 1, foreign_gzip: Optional[str] = None):
+        super().__init__()
+        if int(batch_size) < 1:
+            raise ValueError(f"batch_size must be positive, got {batch_size}")
+        if int(shuffle_window) < 0:
+            raise ValueError(
+                f"shuffle_window must be >= 0, got {shuffle_window}")
+        self.batch_size = int(batch_size)
+        self.shuffle_window = int(shuffle_window)
+        self.seed = int(seed)
+        self.drop_last = bool(drop_last)
+        self.epoch = 0
+        self.truncated_rows = 0
+        self.last_stats = {"batches": 0, "launches": 0, "host_waits": 0}
+        self._init_source(path, schema, record_type, engine, verify_crc,
+                          prefetch, foreign_gzip)
+        self.features = dict(features)
+        plan_columns(self.schema, self.features)  # pairing errors, up front
+
+    def set_epoch(self, epoch: int):
+        self.epoch = int(epoch)
+
+    def _rng(self) -> np.random.Generator:
+        rank = 0
+        try:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized():
+                rank = dist.get_rank()
+        except Exception:
+            pass
+        info = torch.utils.data.get_worker_info()
+        return np.random.default_rng(
+            [self.seed, self.epoch, rank, info.id if info is not None else 0])
+
+    def __iter__(self) -> Iterator[Dict[str, torch.Tensor]]:
+        eng = engine_mod.resolve_engine(self.engine)
+        sub_schema = StructType([f for f in self.schema.fields
+                                 if f.name in self.features])
+        co = Collator(sub_schema, self.features, eng)
+        rng = self._rng()
+        shuffle = self.shuffle_window > 0
+        width = max(self.shuffle_window, 1)
+        shards = self._decoded_shards(eng, sub_schema)
+        live: List[_Slot] = []   # table order; retired slots stay to the
+        dirty = True             # end of the batch that still reads them
+        self.truncated_rows = 0
+        stats = self.last_stats = {"batches": 0, "launches": 0,
+                                   "host_waits": 0}
+
+        def refill():
+            nonlocal dirty
+            while sum(not s.retired for s in live) < width:
+                nxt = next(shards, None)
+                if nxt is None:
+                    return
+                fpath, batch = nxt
+                if eng == "gpu":
+                    from .engine import gpu as gpu_engine
+                    if not all(isinstance(c.presence, torch.Tensor)
+                               and c.presence.is_cuda for c in batch.columns):
+                        # a shard the host decoded (codec fallback)
+                        batch = gpu_engine.batch_to_device(batch)
+                perm = (rng.permutation(batch.num_rows) if shuffle
+                        else np.arange(batch.num_rows, dtype=np.int64))
+                live.append(_Slot(fpath, batch, perm.astype(np.int64)))
+                dirty = True
+
+        def finish(handle, slot, row, paths):
+            outs, (st0, trunc) = co.finish(handle)
+            if st0 != STATUS_CLEAN:
+                b = st0 >> 16
+                raise ValueError(
+                    co.describe_error(st0, slot, row)
+                    + f": shard {paths[int(slot[b])]}, row {int(row[b])}")
+            self.truncated_rows += trunc
+            stats["batches"] += 1
+            stats["launches"] = co.launches
+            stats["host_waits"] = co.host_waits
+            return outs
+
+        pending = None
+        newest = None  # the last launch; the stream runs them in order
+        try:
+            refill()
+            while True:
+                sel_slot: List[np.ndarray] = []
+                sel_row: List[np.ndarray] = []
+                need = self.batch_size
+                while need:
+                    active = [i for i, s in enumerate(live) if not s.retired]
+                    if not active:
+                        break
+                    left = np.array([live[i].left for i in active], np.int64)
+                    k = min(need, int(left.sum()))
+                    counts = (rng.multivariate_hypergeometric(left, k)
+                              if len(active) > 1 else np.array([k]))
+                    for i, n in zip(active, counts):
+                        s = live[i]
+                        n = int(n)
+                        if n:
+                            sel_slot.append(np.full(n, i, np.int32))
+                            sel_row.append(s.perm[s.cursor:s.cursor + n])
+                            s.cursor += n
+                        if s.left == 0:
+                            s.retired = True
+                    need -= k
+                    refill()
+                if not sel_slot:
+                    break
+                slot = np.concatenate(sel_slot)
+                row = np.concatenate(sel_row)
+                if need and self.drop_last:
+                    break
+                if shuffle:
+                    order = rng.permutation(slot.size)
+                    slot, row = slot[order], row[order]
+                if dirty:
+                    co.set_window([s.batch for s in live])
+                    dirty = False
+                handle = newest = co.launch(slot, row)
+                paths = [s.path for s in live]
+                # a launched batch keeps its window alive, so the retired slots
+                # can leave the table now; they are freed after its wait
+                if any(s.retired for s in live):
+                    live[:] = [s for s in live if not s.retired]
+                    dirty = True
+                # one batch ahead: this batch was drawn and launched while the
+                # previous one ran; now wait for that one and hand it out
+                if pending is not None:
+                    yield finish(*pending)
+                pending = (handle, slot, row, paths)
+            if pending is not None:
+                yield finish(*pending)
+        finally:
+            # leaving early (an error, or the consumer stopped): nothing may
+            # be freed under a kernel that still reads it
+            if newest is not None:
+                co.abandon(newest)
