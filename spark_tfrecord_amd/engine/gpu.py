@@ -19,7 +19,7 @@ from __future__ import annotations
 import os
 import threading
 import warnings
-from typing import List, Optional
+from typing import List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -181,6 +181,49 @@ def _read_file_staged(path: str, dev: torch.Tensor) -> torch.Tensor:
     finally:
         os.close(fd)
     return dev
+
+
+def _upload_files(dst: torch.Tensor, entries):
+    """Whole files -> their slices of `dst`: entries = [(path, nbytes,
+    dst_offset)], zero-length files skipped. Each file DMAs from the page
+    cache (pinned mmap) on one of the side streams, or comes through the
+    staged read where its mapping cannot be pinned; the main stream then
+    waits for every side stream used. A side stream first waits for the
+    main stream: `dst` is usually fresh from the caching allocator, which
+    may hand back memory that an earlier main-stream kernel still reads.
+    This is the one upload of every multi-file read. The raw branch of
+    read_files_to_batch once had its own copy that left this wait out, so
+    its copies could race such a kernel."""
+    main = torch.cuda.current_stream()
+    streams = _dma_streams()
+    used = []
+    for k, (path, nbytes, off) in enumerate(entries):
+        if not nbytes:
+            continue
+        ptr, pinned = _native.file_mmap_pinned(path, nbytes, False)
+        if pinned:
+            st = streams[k % len(streams)]
+            st.wait_stream(main)
+            _native.gpu_memcpy_h2d(dst.data_ptr() + off, ptr, nbytes,
+                                   st.cuda_stream)
+            used.append(st)
+        else:
+            _read_file_staged(path, dst[off:off + nbytes])
+    for st in set(used):
+        main.wait_stream(st)
+
+
+def _upload_group(items, device):
+    """The files of a group's items [(path, ...)] back to back in one fresh
+    device buffer: (buffer, each file's offset in it, each file's size)."""
+    sizes = [os.path.getsize(it[0]) for it in items]
+    offs = [0]
+    for n in sizes[:-1]:
+        offs.append(offs[-1] + n)
+    total = sum(sizes)
+    comp = torch.empty(max(total, 1), dtype=torch.uint8, device=device)[:total]
+    _upload_files(comp, [(it[0], n, o) for it, n, o in zip(items, sizes, offs)])
+    return comp, offs, sizes
 
 
 def device_to_file(img: torch.Tensor, path: str):
@@ -1249,29 +1292,13 @@ def _device_inflate_group(data: torch.Tensor, gz_items, device) -> bool:
     the caller redoes those files on host zlib. The gzip CRC32 trailer is
     NOT checked here: the TFRecord layer CRC32C-verifies every record of the
     inflated bytes (a corrupt stream also breaks the frame chain)."""
-    comp_sizes = [os.path.getsize(p) for p, _, _ in gz_items]
-    comp_total = sum(comp_sizes)
-    comp = torch.empty(max(comp_total, 1), dtype=torch.uint8,
-                       device=device)[:comp_total]
-    main = torch.cuda.current_stream()
-    streams = _dma_streams()
+    comp, comp_offs, _ = _upload_group(gz_items, device)
     in_off = []
     in_len = []
     out_off = []
     out_len = []
-    used = []
-    coff = 0
-    for k, (p, meta, out_base) in enumerate(gz_items):
+    for (p, meta, out_base), coff in zip(gz_items, comp_offs):
         body_off, segs, _crc, _isize = meta
-        ptr, pinned = _native.file_mmap_pinned(p, comp_sizes[k], False)
-        if pinned:
-            st = streams[k % len(streams)]
-            st.wait_stream(main)
-            _native.gpu_memcpy_h2d(comp.data_ptr() + coff, ptr, comp_sizes[k],
-                                   st.cuda_stream)
-            used.append(st)
-        else:
-            _read_file_staged(p, comp[coff:coff + comp_sizes[k]])
         so = coff + body_off
         uo = out_base
         for c, u in segs:
@@ -1281,9 +1308,6 @@ def _device_inflate_group(data: torch.Tensor, gz_items, device) -> bool:
             out_len.append(u)
             so += c
             uo += u
-        coff += comp_sizes[k]
-    for st in set(used):
-        main.wait_stream(st)
     # Route each segment to the kernel shape its data favors (measured,
     # profiles/RESULTS.md): literal-heavy segments — compression ratio near
     # 1, every output byte is one Huffman symbol — run ~20% faster TWO per
@@ -1315,21 +1339,6 @@ def _device_inflate_group(data: torch.Tensor, gz_items, device) -> bool:
             sub[2].data_ptr(), sub[3].data_ptr(), k,
             data.data_ptr(), err.data_ptr(), _stream(), spw)
     return int(err.item()) == -1
-
-
-def read_gzip_file_to_device(path: str, device="cuda") -> Optional[torch.Tensor]:
-    """Our-format gzip file -> decompressed bytes in HBM via the device
-    inflater. None when the file carries no segment table or the kernel
-    rejected a segment (callers fall back to host zlib)."""
-    meta = gz_device_meta(path)
-    if meta is None:
-        return None
-    total_u = sum(u for _, u in meta[1])
-    data = torch.empty(max(total_u, 1), dtype=torch.uint8,
-                       device=device)[:total_u]
-    if not _device_inflate_group(data, [(path, meta, 0)], device):
-        return None
-    return data
 
 
 class DeviceDecompressRejected(Exception):
@@ -1450,41 +1459,24 @@ def _device_inflate_foreign_group(data: torch.Tensor, items, device,
     piece = int(_native.FOREIGN_CRC_PIECE)
     ok_all = []
     del last_foreign[:]
-    main = torch.cuda.current_stream()
-    streams = _dma_streams()
     for lo in range(0, len(items), _FOREIGN_MAX_FILES):
         part = items[lo:lo + _FOREIGN_MAX_FILES]
         nfile = len(part)
-        comp_sizes = [os.path.getsize(p) for p, _, _ in part]
-        comp_total = sum(comp_sizes)
-        comp = torch.empty(comp_total, dtype=torch.uint8, device=device)
+        comp, comp_offs, comp_sizes = _upload_group(part, device)
         ft = np.zeros((nfile, FC), np.int64)
-        coff = chunk0 = sym0 = piece0 = 0
-        used = []
+        chunk0 = sym0 = piece0 = 0
         for k, (p, meta, out_base) in enumerate(part):
             body_off, body_len, crc, isize = meta
             if (body_off + body_len + 8 != comp_sizes[k] or out_base < 0
                     or out_base + isize > data.numel()):
                 raise ValueError(f"foreign gzip extents changed under the "
                                  f"read: {p}")
-            ptr, pinned = _native.file_mmap_pinned(p, comp_sizes[k], False)
-            if pinned:
-                st = streams[k % len(streams)]
-                st.wait_stream(main)
-                _native.gpu_memcpy_h2d(comp.data_ptr() + coff, ptr,
-                                       comp_sizes[k], st.cuda_stream)
-                used.append(st)
-            else:
-                _read_file_staged(p, comp[coff:coff + comp_sizes[k]])
             nchunk = -(-body_len // chunk)
-            ft[k, :9] = (coff + body_off, body_len, isize, crc, chunk0, nchunk,
-                         out_base, sym0, piece0)
-            coff += comp_sizes[k]
+            ft[k, :9] = (comp_offs[k] + body_off, body_len, isize, crc, chunk0,
+                         nchunk, out_base, sym0, piece0)
             chunk0 += nchunk
             sym0 += isize
             piece0 += -(-isize // piece)
-        for st in set(used):
-            main.wait_stream(st)
         # chunk table rows: file, start -1, len 0, end 0, next -2 (none),
         # rc 0, out_off -1 (not live), live-list slot
         ct = np.zeros((chunk0, CC), np.int64)
@@ -1510,25 +1502,6 @@ def _device_inflate_foreign_group(data: torch.Tensor, items, device,
             last_foreign.append((p, int(out[k, 1]), int(out[k, 3]),
                                  int(out[k, 0])))
     return ok_all
-
-
-def read_foreign_gzip_file_to_device(path: str,
-                                     chunk_bytes: Optional[int] = None,
-                                     device="cuda") -> Optional[torch.Tensor]:
-    """Any single-member gzip file -> decompressed bytes in HBM via the
-    speculative device inflater, CRC-32 checked. None when the file is not
-    eligible (foreign_gz_meta) or the inflater refused it: multi-member,
-    truncated, corrupt, CRC or ISIZE mismatch (callers fall back to host
-    zlib)."""
-    check_native()
-    meta = foreign_gz_meta(path)
-    if meta is None:
-        return None
-    data = torch.empty(meta[3], dtype=torch.uint8, device=device)
-    if not _device_inflate_foreign_group(data, [(path, meta, 0)], device,
-                                         chunk_bytes)[0]:
-        return None
-    return data
 
 
 # what the last device Snappy decode did, per file: [(path, chunks, error
@@ -1603,22 +1576,16 @@ def _device_unsnap_group(data: torch.Tensor, items, device):
     (the slice's content is unspecified), read the file on the host."""
     del last_snappy[:]
     nfile = len(items)
-    comp_sizes = [os.path.getsize(p) for p, _, _ in items]
-    comp_total = sum(comp_sizes)
-    comp = torch.empty(max(comp_total, 1), dtype=torch.uint8,
-                       device=device)[:comp_total]
-    main = torch.cuda.current_stream()
-    streams = _dma_streams()
+    comp, comp_offs, comp_sizes = _upload_group(items, device)
     tables = []
     chunk0 = np.zeros(nfile, np.int64)
-    coff = nchunk = 0
-    used = []
+    nchunk = 0
     for k, (p, meta, out_base) in enumerate(items):
         ext, total = meta
         chunk0[k] = nchunk
         if ext.shape[0]:
             t = np.empty((ext.shape[0], 5), np.int64)
-            t[:, 0] = ext[:, 0] + coff
+            t[:, 0] = ext[:, 0] + comp_offs[k]
             t[:, 1] = ext[:, 1]
             t[:, 2] = ext[:, 2] + out_base
             t[:, 3] = ext[:, 3]
@@ -1632,19 +1599,6 @@ def _device_unsnap_group(data: torch.Tensor, items, device):
                 raise ValueError(f"snappy extents changed under the read: {p}")
             tables.append(t)
             nchunk += ext.shape[0]
-        if comp_sizes[k]:
-            ptr, pinned = _native.file_mmap_pinned(p, comp_sizes[k], False)
-            if pinned:
-                st = streams[k % len(streams)]
-                st.wait_stream(main)
-                _native.gpu_memcpy_h2d(comp.data_ptr() + coff, ptr,
-                                       comp_sizes[k], st.cuda_stream)
-                used.append(st)
-            else:
-                _read_file_staged(p, comp[coff:coff + comp_sizes[k]])
-        coff += comp_sizes[k]
-    for st in set(used):
-        main.wait_stream(st)
     err = np.full(nfile, -1, np.int64)
     if nchunk:
         assert int(_native.SNAPPY_CHUNK_COLS) == 5
@@ -1663,20 +1617,106 @@ def _device_unsnap_group(data: torch.Tensor, items, device):
     return ok
 
 
+class DeviceSource(NamedTuple):
+    """Where a file's bytes come from when the device takes it."""
+    kind: str    # "raw" | "gzip" | "foreign" | "snappy"
+    meta: object  # what the kind's *_meta function returned; None for raw
+    nbytes: int  # decompressed length
+
+
+def _gzip_source(path: str) -> Optional[DeviceSource]:
+    meta = gz_device_meta(path)
+    if meta is None:
+        return None
+    return DeviceSource("gzip", meta, sum(u for _, u in meta[1]))
+
+
+def _foreign_source(path: str) -> Optional[DeviceSource]:
+    meta = foreign_gz_meta(path)
+    return None if meta is None else DeviceSource("foreign", meta, meta[3])
+
+
+def _snappy_source(path: str) -> Optional[DeviceSource]:
+    meta = snappy_device_meta(path)
+    return None if meta is None else DeviceSource("snappy", meta, meta[1])
+
+
+def device_source(path: str,
+                  foreign_gzip: bool = False) -> Optional[DeviceSource]:
+    """THE place that decides where a file's bytes come from: a raw DMA,
+    the segment-table inflater (our gzip), the speculative inflater (any
+    other writer's gzip, only with `foreign_gzip`, and only after the
+    segment table was looked for), the Snappy decoder, or, None, the host
+    codec. Every read path asks here, once per file, and hands the answer
+    on (read_files_to_batch `sources=`), so a file's header is walked once
+    per read."""
+    from ..io import paths as P
+
+    codec = P.codec_from_path(path)
+    if codec is None:
+        return DeviceSource("raw", None, os.path.getsize(path))
+    if codec == "gzip":
+        return _gzip_source(path) or (_foreign_source(path) if foreign_gzip
+                                      else None)
+    if codec == "snappy":
+        return _snappy_source(path)
+    return None
+
+
+def _source_image(path: str, src: Optional[DeviceSource], device,
+                  chunk_bytes: Optional[int] = None) -> Optional[torch.Tensor]:
+    """The bytes of one file in HBM, through the decoder `src` names. None
+    when there is no source or the decoder refused the file (callers fall
+    back to the host codec)."""
+    if src is None:
+        return None
+    if src.kind == "raw":
+        return read_file_to_device(path, device)
+    data = torch.empty(max(src.nbytes, 1), dtype=torch.uint8,
+                       device=device)[:src.nbytes]
+    items = [(path, src.meta, 0)]
+    if src.kind == "gzip":
+        ok = _device_inflate_group(data, items, device)
+    elif src.kind == "foreign":
+        ok = _device_inflate_foreign_group(data, items, device, chunk_bytes)[0]
+    else:
+        ok = _device_unsnap_group(data, items, device)[0]
+    return data if ok else None
+
+
+def read_file_image(path: str, foreign_gzip: bool = False,
+                    device="cuda") -> Optional[torch.Tensor]:
+    """Any file device_source accepts -> its (decompressed) bytes in HBM.
+    None when the file is for the host or the device refused it."""
+    return _source_image(path, device_source(path, foreign_gzip), device)
+
+
+def read_gzip_file_to_device(path: str, device="cuda") -> Optional[torch.Tensor]:
+    """Our-format gzip file -> decompressed bytes in HBM via the device
+    inflater. None when the file carries no segment table or the kernel
+    rejected a segment (callers fall back to host zlib)."""
+    return _source_image(path, _gzip_source(path), device)
+
+
+def read_foreign_gzip_file_to_device(path: str,
+                                     chunk_bytes: Optional[int] = None,
+                                     device="cuda") -> Optional[torch.Tensor]:
+    """Any single-member gzip file -> decompressed bytes in HBM via the
+    speculative device inflater, CRC-32 checked. None when the file is not
+    eligible (foreign_gz_meta) or the inflater refused it: multi-member,
+    truncated, corrupt, CRC or ISIZE mismatch (callers fall back to host
+    zlib)."""
+    check_native()
+    return _source_image(path, _foreign_source(path), device, chunk_bytes)
+
+
 def read_snappy_file_to_device(path: str,
                                device="cuda") -> Optional[torch.Tensor]:
     """`.snappy` file -> decompressed bytes in HBM via the device decoder.
     None when the file is not eligible (snappy_device_meta) or the kernel
     refused a chunk (callers fall back to the host codec)."""
     check_native()
-    meta = snappy_device_meta(path)
-    if meta is None:
-        return None
-    total = meta[1]
-    data = torch.empty(max(total, 1), dtype=torch.uint8, device=device)[:total]
-    if not _device_unsnap_group(data, [(path, meta, 0)], device)[0]:
-        return None
-    return data
+    return _source_image(path, _snappy_source(path), device)
 
 
 def _deflate_max_waves(device) -> int:
@@ -1742,7 +1782,7 @@ def gzip_image_device(img: torch.Tensor, seg: Optional[int] = None) -> torch.Ten
 
 def read_files_to_batch(paths, schema: StructType, record_type: str,
                         verify_crc: bool = True, device="cuda",
-                        foreign_gzip: bool = False):
+                        foreign_gzip: bool = False, sources=None):
     """Decode MANY files as ONE GPU pipeline: their (decompressed) images
     are concatenated in HBM (TFRecord frames are concatenable, so the frame
     chain spans file boundaries exactly), scanned and decoded once, and the
@@ -1754,43 +1794,23 @@ def read_files_to_batch(paths, schema: StructType, record_type: str,
     names those it refuses. With `foreign_gzip`, gzip files without the
     table go through the speculative inflater into their own slices of the
     same image; if it refuses any, ForeignGzipRejected names them and
-    nothing is decoded. Returns (device RecordBatch, np.ndarray row_counts
-    per file)."""
+    nothing is decoded. `sources` hands over each path's device_source
+    record where the caller already has it; without it the files are
+    classified here. Returns (device RecordBatch, np.ndarray row_counts per
+    file)."""
     from ..io import paths as P
 
     check_native()
-    metas = []
-    fmetas = []
-    smetas = []
-    sizes = []
-    for p in paths:
-        if P.codec_from_path(p) == "snappy":
-            smeta = snappy_device_meta(p)
-            if smeta is None:
-                raise ValueError(f"snappy file not for the device decoder: "
-                                 f"{p} (host path required)")
-            metas.append(None)
-            fmetas.append(None)
-            smetas.append(smeta)
-            sizes.append(smeta[1])
-            continue
-        smetas.append(None)
-        if P.codec_from_path(p) == "gzip":
-            meta = P.parse_gz_segments_file(p)
-            fmeta = None
-            if meta is None and foreign_gzip:
-                fmeta = foreign_gz_meta(p)
-            if meta is None and fmeta is None:
-                raise ValueError(f"gzip file without segment table: {p} "
-                                 "(host path required)")
-            metas.append(meta)
-            fmetas.append(fmeta)
-            sizes.append(sum(u for _, u in meta[1]) if meta is not None
-                         else fmeta[3])
-        else:
-            metas.append(None)
-            fmetas.append(None)
-            sizes.append(os.path.getsize(p))
+    if sources is None:
+        sources = [device_source(p, foreign_gzip) for p in paths]
+    for p, src in zip(paths, sources):
+        if src is None:
+            what = {"gzip": "gzip file without segment table",
+                    "snappy": "snappy file not for the device decoder"}
+            raise ValueError(
+                f"{what.get(P.codec_from_path(p), 'file not for the device')}"
+                f": {p} (host path required)")
+    sizes = [src.nbytes for src in sources]
     n = sum(sizes)
     if n == 0:
         if schema is None:
@@ -1803,31 +1823,17 @@ def read_files_to_batch(paths, schema: StructType, record_type: str,
     data = torch.empty(n, dtype=torch.uint8, device=device)
     bounds = np.zeros(len(paths) + 1, np.int64)
     np.cumsum(sizes, out=bounds[1:])
-    main = torch.cuda.current_stream()
-    streams = _dma_streams()
-    gz_items = []
-    foreign_items = []
-    snappy_items = []
-    for i, p in enumerate(paths):
-        if not sizes[i]:
-            continue
-        if smetas[i] is not None:
-            snappy_items.append((p, smetas[i], int(bounds[i])))
-            continue
-        if metas[i] is not None:
-            gz_items.append((p, metas[i], int(bounds[i])))
-            continue
-        if fmetas[i] is not None:
-            foreign_items.append((p, fmetas[i], int(bounds[i])))
-            continue
-        ptr, pinned = _native.file_mmap_pinned(p, sizes[i], False)
-        if pinned:
-            st = streams[i % len(streams)]
-            _native.gpu_memcpy_h2d(data.data_ptr() + int(bounds[i]), ptr,
-                                   sizes[i], st.cuda_stream)
-            main.wait_stream(st)
-        else:
-            _read_file_staged(p, data[int(bounds[i]):int(bounds[i + 1])])
+    # each non-empty file with its slice of the image, bucketed by kind
+    raw_files = []
+    items = {"gzip": [], "foreign": [], "snappy": []}
+    for p, src, base in zip(paths, sources, bounds):
+        if src.kind == "raw":
+            raw_files.append((p, src.nbytes, int(base)))
+        elif src.nbytes:
+            items[src.kind].append((p, src.meta, int(base)))
+    gz_items, foreign_items, snappy_items = (
+        items["gzip"], items["foreign"], items["snappy"])
+    _upload_files(data, raw_files)
     if foreign_items:
         ok = _device_inflate_foreign_group(data, foreign_items, device)
         refused = [it[0] for it, good in zip(foreign_items, ok) if not good]

@@ -60,57 +60,42 @@ def _load_file(path: str) -> np.ndarray:
     return np.frombuffer(P.decompress_file(path), np.uint8)
 
 
+def _scanned_files(files: List[str], eng: str):
+    """(image, frame offsets, frame lengths) of each non-empty file, in
+    order: device tensors where the GPU engine takes the file
+    (gpu.device_source, foreign gzip left to the host), numpy arrays of the
+    host codec's bytes otherwise."""
+    for f in files:
+        if eng == "gpu" and os.path.getsize(f):
+            from ..engine import gpu as gpu_engine
+
+            data = gpu_engine.read_file_image(f)
+            if data is not None:
+                if data.numel():
+                    yield (data, *gpu_engine.scan_frames_device(data))
+                continue
+        data = _load_file(f)
+        if data.size:
+            yield (data, *_native.scan_frames(data, False))
+
+
 def infer_schema_of_paths(files: List[str], record_type: str,
                           engine: str = "cpu") -> StructType:
     """Schema from the FIRST non-empty file (DefaultSource.scala:36-38
     collectFirst), scanned fully — on the GPU (hash-table lattice kernel)
-    when engine='gpu' and the file is uncompressed."""
+    when engine='gpu' and the device takes the file."""
     if record_type == "ByteArray":
         return byte_array_schema()
-    for f in files:
-        if engine == "gpu" and P.codec_from_path(f) in (None, "gzip",
-                                                        "snappy"):
-            import os as _os
-
-            if _os.path.getsize(f) == 0:
-                continue
+    for data, off, lens in _scanned_files(files, engine):
+        if len(off) == 0:
+            continue
+        if isinstance(data, np.ndarray):
+            codes = infer_codes_from_buffer(data, off, lens, record_type)
+        else:
             from ..engine import gpu as gpu_engine
 
-            if P.codec_from_path(f) in ("gzip", "snappy"):
-                data = (gpu_engine.read_gzip_file_to_device(f)
-                        if P.codec_from_path(f) == "gzip"
-                        else gpu_engine.read_snappy_file_to_device(f))
-                if data is None:  # not for the device: host bytes + lattice
-                    data_np = _load_file(f)
-                    if data_np.size == 0:
-                        continue
-                    off_h, lens_h = _native.scan_frames(data_np, False)
-                    if len(off_h) == 0:
-                        continue
-                    codes = infer_codes_from_buffer(data_np, off_h, lens_h,
-                                                    record_type)
-                    if codes:
-                        return schema_from_codes(codes)
-                    return StructType([])
-                if data.numel() == 0:
-                    continue
-            else:
-                data = gpu_engine.read_file_to_device(f)
-            off, lens = gpu_engine.scan_frames_device(data)
-            if off.numel() == 0:
-                continue
             codes = gpu_engine.infer_codes_device(data, off, lens, record_type)
-        else:
-            data = _load_file(f)
-            if data.size == 0:
-                continue
-            off, lens = _native.scan_frames(data, False)
-            if len(off) == 0:
-                continue
-            codes = infer_codes_from_buffer(data, off, lens, record_type)
-        if codes:
-            return schema_from_codes(codes)
-        return StructType([])
+        return schema_from_codes(codes) if codes else StructType([])
     raise ValueError("Could not infer schema: no non-empty TFRecord files found")
 
 
@@ -141,36 +126,7 @@ def count_tfrecord(path: str, engine: str = "auto") -> int:
     if not files:
         raise FileNotFoundError(f"No TFRecord files found under {path}")
     eng = engine_mod.resolve_engine(engine)
-    total = 0
-    for f in files:
-        if eng == "gpu" and P.codec_from_path(f) in (None, "gzip", "snappy"):
-            if os.path.getsize(f) == 0:
-                continue
-            from ..engine import gpu as gpu_engine
-
-            if P.codec_from_path(f) in ("gzip", "snappy"):
-                data = (gpu_engine.read_gzip_file_to_device(f)
-                        if P.codec_from_path(f) == "gzip"
-                        else gpu_engine.read_snappy_file_to_device(f))
-                if data is None:  # foreign gzip / refused snappy: host count
-                    data_np = _load_file(f)
-                    if data_np.size:
-                        off_h, _ = _native.scan_frames(data_np, False)
-                        total += len(off_h)
-                    continue
-                if data.numel() == 0:
-                    continue
-            else:
-                data = gpu_engine.read_file_to_device(f)
-            off, _ = gpu_engine.scan_frames_device(data)
-            total += int(off.numel())
-        else:
-            data = _load_file(f)
-            if data.size == 0:
-                continue
-            off, _ = _native.scan_frames(data, False)
-            total += len(off)
-    return total
+    return sum(len(off) for _, off, _ in _scanned_files(files, eng))
 
 
 def read_tfrecord(path: str, schema: Optional[StructType] = None,
@@ -204,7 +160,8 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
     part_cols = _partition_schema(files, base_dir) if base_dir else []
     eng = engine_mod.resolve_engine(engine)
     foreign_device = _resolve_foreign_gzip(foreign_gzip, eng)
-    host_only: set = set()  # compressed files the device refused
+    if eng == "gpu":
+        from ..engine import gpu as gpu_engine
 
     metrics = IOMetrics("read")
 
@@ -215,49 +172,26 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
     # bounds resident decompressed bytes.
     from concurrent.futures import ThreadPoolExecutor
 
-    _host_bytes_memo: dict = {}
+    # path -> gpu.device_source record, None = host bytes; each file is
+    # classified once per read (its header or block table walked once), and
+    # a file the device then refuses is set to None
+    sources: dict = {}
 
-    def _needs_host_bytes(fpath: str) -> bool:
-        if fpath in host_only:
-            return True
-        if fpath not in _host_bytes_memo:  # asked several times per file
-            _host_bytes_memo[fpath] = _needs_host_bytes_uncached(fpath)
-        return _host_bytes_memo[fpath]
-
-    def _needs_host_bytes_uncached(fpath: str) -> bool:
-        if eng != "gpu":
-            return True
-        codec = P.codec_from_path(fpath)
-        if codec is None:
-            return False
-        if codec == "gzip":
-            # our gzip files carry a segment table: the device inflater
-            # decompresses them in HBM (foreign gzip stays on host zlib)
-            from ..engine import gpu as gpu_engine
-            if gpu_engine.gz_device_meta(fpath) is not None:
-                return False
-            # any other writer's gzip: the speculative inflater, if asked
-            # for and the file is eligible
-            return not (foreign_device
-                        and gpu_engine.foreign_gz_meta(fpath) is not None)
-        if codec == "snappy":
-            # the block headers give every chunk's extents: the device
-            # decoder takes the file unless the walk fails, a chunk is over
-            # its cap, or TFREC_SNAPPY=host
-            from ..engine import gpu as gpu_engine
-            return gpu_engine.snappy_device_meta(fpath) is None
-        return True
+    def _source(fpath: str):
+        if fpath not in sources:
+            sources[fpath] = (gpu_engine.device_source(fpath, foreign_device)
+                              if eng == "gpu" else None)
+        return sources[fpath]
 
     # Schema-less GPU reads DEFER inference into the first group pipeline:
     # the file image is scanned once in HBM, the lattice kernel runs over
     # the first non-empty file's frames, and the decode reuses the image —
     # one pass instead of the reference's extra inference job.
     deferred_infer = (schema is None and eng == "gpu" and bool(files)
-                      and not _needs_host_bytes(files[0]))
+                      and _source(files[0]) is not None)
     if schema is None and not deferred_infer:
         with StageTimer(metrics, "infer_schema"):
-            schema = (byte_array_schema() if record_type == "ByteArray"
-                      else infer_schema_of_paths(files, record_type, eng))
+            schema = infer_schema_of_paths(files, record_type, eng)
 
     def _resolve(schema):
         nonlocal part_cols
@@ -311,6 +245,17 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
     # files and the CPU engine go file-by-file through host bytes.
     _GROUP_BYTES = 4 << 30
 
+    def _read_group(group, schema):
+        """One pipeline over the group's files; schema None = infer it from
+        the group's first non-empty file on the way."""
+        return gpu_engine.read_files_to_batch(
+            group, schema, record_type, verify_crc=verify_crc,
+            foreign_gzip=foreign_device, sources=[sources[f] for f in group])
+
+    def _infer_from_files():
+        """The fallback where no group could infer: from the whole list."""
+        return _resolve(infer_schema_of_paths(files, record_type, eng))
+
     def _append_with_parts(t, fpaths, row_counts):
         pvs = [P.partition_values_of(f, base_dir) for f in fpaths]
         for c in part_cols:
@@ -323,13 +268,11 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
         i = 0
         while i < len(files):
             fpath = files[i]
-            if eng == "gpu" and not _needs_host_bytes(fpath):
-                from ..engine import gpu as gpu_engine
-
+            if _source(fpath) is not None:
                 group = []
                 gbytes = 0
                 i0 = i
-                while (i < len(files) and not _needs_host_bytes(files[i])
+                while (i < len(files) and _source(files[i]) is not None
                        and gbytes < _GROUP_BYTES):
                     group.append(files[i])
                     gbytes += os.path.getsize(files[i])
@@ -337,28 +280,16 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
                 try:
                     if data_schema is None:
                         try:
-                            batch, row_counts = gpu_engine.read_files_to_batch(
-                                group, None, record_type,
-                                verify_crc=verify_crc,
-                                foreign_gzip=foreign_device)
+                            batch, row_counts = _read_group(group, None)
                             data_schema = _resolve(batch.schema)
                         except ValueError:
                             # this group was entirely empty: resolve the
                             # schema from the full file list, then decode
                             # normally
-                            data_schema = _resolve(
-                                byte_array_schema()
-                                if record_type == "ByteArray"
-                                else infer_schema_of_paths(files, record_type,
-                                                           eng))
-                            batch, row_counts = gpu_engine.read_files_to_batch(
-                                group, data_schema, record_type,
-                                verify_crc=verify_crc,
-                                foreign_gzip=foreign_device)
+                            data_schema = _infer_from_files()
+                            batch, row_counts = _read_group(group, data_schema)
                     else:
-                        batch, row_counts = gpu_engine.read_files_to_batch(
-                            group, data_schema, record_type,
-                            verify_crc=verify_crc, foreign_gzip=foreign_device)
+                        batch, row_counts = _read_group(group, data_schema)
                 except gpu_engine.DeviceDecompressRejected as rej:
                     # redo the group without the refused files: they take
                     # the host path, as with foreign_gzip="host" (gzip) or
@@ -366,6 +297,7 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
                     import logging
 
                     for p in rej.paths:
+                        sources[p] = None  # host bytes from here on
                         if isinstance(rej, gpu_engine.ForeignGzipRejected):
                             logging.getLogger(__name__).warning(
                                 "device inflate refused foreign gzip file "
@@ -374,7 +306,6 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
                             logging.getLogger(__name__).warning(
                                 "device decode refused %s; host codec "
                                 "fallback", p)
-                    host_only.update(rej.paths)
                     i = i0
                     continue
                 for f in group:
@@ -389,22 +320,19 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
                 _append_with_parts(t, group, row_counts)
                 continue
             for j in range(i, min(i + window, len(files))):
-                if (not _inline_small and _needs_host_bytes(files[j])
+                if (not _inline_small and _source(files[j]) is None
                         and j not in futures):
                     futures[j] = _pool().submit(_host_task, files[j])
             metrics.add(files=1, nbytes=os.path.getsize(fpath))
             if data_schema is None:
                 # inference was deferred to a group the device then refused
                 with StageTimer(metrics, "infer_schema"):
-                    data_schema = _resolve(
-                        byte_array_schema() if record_type == "ByteArray"
-                        else infer_schema_of_paths(files, record_type, eng))
+                    data_schema = _infer_from_files()
             got = _blob(i)
             i += 1
             if eng == "gpu":
                 if got.size == 0:
                     continue
-                from ..engine import gpu as gpu_engine
                 batch = gpu_engine.decode_buffer_to_cpu(
                     got, data_schema, record_type, verify_crc=verify_crc)
             else:

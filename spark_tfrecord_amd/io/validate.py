@@ -52,22 +52,13 @@ class ValidationReport:
 def _validate_one(fpath: str, eng: str) -> FileReport:
     size = os.path.getsize(fpath)
     try:
-        if eng == "gpu" and P.codec_from_path(fpath) in (None, "gzip",
-                                                         "snappy"):
-            if size == 0:
-                return FileReport(fpath, 0, 0, True)
+        if eng == "gpu" and size:
             from ..engine import gpu as gpu_engine
 
-            if P.codec_from_path(fpath) == "gzip":
-                # device inflate for our table-bearing gzip; None (foreign
-                # gzip) drops through to the host path
-                data = gpu_engine.read_gzip_file_to_device(fpath)
-            elif P.codec_from_path(fpath) == "snappy":
-                # device Snappy decode; None (malformed, refused, or
-                # TFREC_SNAPPY=host) drops through to the host path
-                data = gpu_engine.read_snappy_file_to_device(fpath)
-            else:
-                data = gpu_engine.read_file_to_device(fpath)
+            # None (a file for the host codec: foreign gzip, deflate,
+            # TFREC_SNAPPY=host, or one the device refused) drops through
+            # to the host path
+            data = gpu_engine.read_file_image(fpath)
             if data is not None:
                 if data.numel() == 0:
                     return FileReport(fpath, 0, size, True)

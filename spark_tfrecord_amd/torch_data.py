@@ -145,19 +145,11 @@ class _ShardSource(torch.utils.data.IterableDataset):
                 fpath, sub_schema, self.record_type, self.verify_crc)
             torch.cuda.current_stream().synchronize()  # hand off across threads
             return batch
-        if eng == "gpu" and P.codec_from_path(fpath) in ("gzip", "snappy"):
-            # our gzip shards inflate ON the training GPU (segment table),
-            # snappy shards decode there (None -> host codec below)
+        if eng == "gpu":
+            # compressed shards the device takes (gpu.device_source) inflate
+            # or decode ON the training GPU; None -> host codec below
             from .engine import gpu as gpu_engine
-            if P.codec_from_path(fpath) == "snappy":
-                dev = gpu_engine.read_snappy_file_to_device(fpath)
-            else:
-                dev = gpu_engine.read_gzip_file_to_device(fpath)
-            if (dev is None and self._foreign_device
-                    and P.codec_from_path(fpath) == "gzip"):
-                # no segment table: the speculative inflater (None again
-                # for a file it refuses -> host zlib below)
-                dev = gpu_engine.read_foreign_gzip_file_to_device(fpath)
+            dev = gpu_engine.read_file_image(fpath, self._foreign_device)
             if dev is not None:
                 if dev.numel() == 0:
                     return None
