@@ -19,6 +19,9 @@ driver runs it). This suite covers the rest, each printing one JSON line:
                   level 6, no segment table): host zlib pool vs the
                   speculative device inflater (foreign_gzip="host" |
                   "device"), as one file and as 32 files
+  snappy_write    GPU-engine snappy write of flagship rows, pyarrow's Snappy
+                  on the host vs the device compressor (snappy_engine="host"
+                  | "device"), as 1 shard and as 8 shards
   gzip_bytearray  config 5: gzip-compressed ByteArray read, shard staged
                   through HBM on the GPU engine
   collate         dense training batches of 8192 flagship rows from 8
@@ -490,6 +493,57 @@ def bench_snappy(args):
     shutil.rmtree(d, ignore_errors=True)
 
 
+def bench_snappy_write(args):
+    """GPU-engine snappy write of --rows flagship Example rows: pyarrow's
+    Snappy on the host (the default) against the device compressor, same
+    build, same data, as 1 shard and as 8 shards. The two engines alternate
+    in one process after a warm-up of each."""
+    import torch
+
+    import spark_tfrecord_amd as stf
+    from spark_tfrecord_amd.io import paths as P
+
+    rank, world = _env_world()
+    if not torch.cuda.is_available():
+        raise SystemExit("snappy_write needs the GPU engine")
+    rows = args.rows // max(world, 1)
+    table = _flagship_table(rows, 7 + rank)
+    d = _workdir("snw", rank)
+    engines = ("host", "device")
+    for shards in (1, 8):
+        outs = {e: os.path.join(d, f"s{shards}_{e}") for e in engines}
+
+        def write(e):
+            stf.write_tfrecord(table, outs[e], record_type="Example",
+                               codec="snappy", mode="overwrite", engine="gpu",
+                               num_shards=shards, snappy_engine=e)
+            torch.cuda.synchronize()
+
+        el = dict.fromkeys(engines, 0.0)
+        for e in engines:
+            write(e)  # warm-up: allocator pools, pinned buffers, page cache
+        for _ in range(args.reps):
+            for e in engines:
+                t0 = time.perf_counter()
+                write(e)
+                el[e] += time.perf_counter() - t0
+        sizes = {e: sum(os.path.getsize(f) for f in P.list_data_files(outs[e]))
+                 for e in engines}
+        got = stf.read_tfrecord(outs["device"], engine="gpu").count()
+        assert got == rows, (got, rows)
+        for e in engines:
+            _emit(rank, f"rows/sec snappy write {shards} shard(s) "
+                        f"snappy_engine={e}",
+                  rows * args.reps / el[e], "rows/s",
+                  {"rows": rows, "shards": shards, "snappy_engine": e,
+                   "snappy_bytes": sizes[e],
+                   "device_over_host": round(el["host"] / el["device"], 3),
+                   "device_over_host_bytes": round(
+                       sizes["device"] / sizes["host"], 4),
+                   "engine": "gpu", "reps": args.reps}, el[e], 1)
+    shutil.rmtree(d, ignore_errors=True)
+
+
 def _torch_collate(batch, lo, hi, torch):
     """The flagship spec (id FixedLen(), ints Padded(8), floats FixedLen(16),
     tokens Padded2D(2, 12)) for rows [lo, hi) of one decoded shard in torch
@@ -670,7 +724,8 @@ BENCHES = {"plumbing": bench_plumbing, "partitionby": bench_partitionby,
            "infer": bench_infer, "gzip_bytearray": bench_gzip_bytearray,
            "gzip_write": bench_gzip_write,
            "gzip_foreign": bench_gzip_foreign,
-           "snappy": bench_snappy, "collate": bench_collate}
+           "snappy": bench_snappy, "snappy_write": bench_snappy_write,
+           "collate": bench_collate}
 
 
 def main():

@@ -20,6 +20,7 @@ SOURCES = [ROOT / "csrc" / "ext.cpp", ROOT / "csrc" / "hip" / "kernels.hip",
            ROOT / "csrc" / "hip" / "deflate.hip",
            ROOT / "csrc" / "hip" / "inflate_foreign.hip",
            ROOT / "csrc" / "hip" / "snappy.hip",
+           ROOT / "csrc" / "hip" / "snappy_enc.hip",
            ROOT / "csrc" / "hip" / "collate.hip"]
 HEADERS = list((ROOT / "csrc").rglob("*.h"))
 

@@ -33,6 +33,7 @@
 #include "inflate_core.h"
 #include "inflate_spec_core.h"
 #include "snappy_core.h"
+#include "snappy_enc_core.h"
 #include "collate_core.h"
 
 namespace py = pybind11;
@@ -831,6 +832,25 @@ py::bytes host_unsnap_chunk(py::buffer comp, i64 expect_len) {
   return py::bytes(out);
 }
 
+// Host run of the raw-Snappy chunk compressor core shared with the gfx950
+// kernel (csrc/snappy_enc_core.h): `lane` < 0 emulates the lanes with loops
+// and is byte-identical to the device, which backs the CPU tests.
+py::bytes host_snap_chunk(py::buffer data) {
+  auto info = data.request();
+  i64 n = static_cast<i64>(info.size * info.itemsize);
+  i64 cap = tfrec::snappy::snap_out_bound(n);
+  std::string out(static_cast<size_t>(cap), '\0');
+  // LDS starts out with whatever the last block left there: the host run
+  // must not lean on zeroed scratch either
+  std::unique_ptr<tfrec::snappy::EncScratch> S(new tfrec::snappy::EncScratch);
+  std::memset(static_cast<void*>(S.get()), 0xA5,
+              sizeof(tfrec::snappy::EncScratch));
+  i64 len = tfrec::snappy::snap_one(static_cast<const u8*>(info.ptr), n,
+                                    reinterpret_cast<u8*>(&out[0]), cap, *S);
+  if (len < 0) throw std::runtime_error("snap_one failed");
+  return py::bytes(out.data(), static_cast<size_t>(len));
+}
+
 // Host run of the batch collation core shared with the gfx950 kernel
 // (csrc/collate_core.h): the same do_unit over every unit of every column,
 // in plain loops. The tables hold host addresses of numpy buffers the caller
@@ -898,6 +918,7 @@ void register_inflate(py::module_& m);  // defined in csrc/hip/inflate.hip
 void register_deflate(py::module_& m);  // defined in csrc/hip/deflate.hip
 void register_inflate_foreign(py::module_& m);  // csrc/hip/inflate_foreign.hip
 void register_snappy(py::module_& m);   // defined in csrc/hip/snappy.hip
+void register_snappy_enc(py::module_& m);  // csrc/hip/snappy_enc.hip
 void register_collate(py::module_& m);  // defined in csrc/hip/collate.hip
 
 PYBIND11_MODULE(_native, m) {
@@ -931,6 +952,12 @@ PYBIND11_MODULE(_native, m) {
         py::arg("expect_len"),
         "TEST-ONLY: run the device Snappy decoder's core on host for one raw "
         "chunk; raises RuntimeError naming the cause code on a refusal");
+  m.def("host_snap_chunk", &host_snap_chunk, py::arg("data"),
+        "TEST-ONLY: run the device Snappy compressor's core on host for one "
+        "block -> its raw chunk");
+  m.def("snappy_out_bound",
+        [](i64 n) { return tfrec::snappy::snap_out_bound(n); },
+        "Staging-slot size for the chunk of an n-byte block");
   m.def("host_collate", &host_collate, py::arg("src"), py::arg("cols"),
         py::arg("sel_slot"), py::arg("sel_row"), py::arg("status"),
         "Collate (slot, row) pairs into the dense outputs of the column "
@@ -970,6 +997,7 @@ PYBIND11_MODULE(_native, m) {
   register_deflate(m);
   register_inflate_foreign(m);
   register_snappy(m);
+  register_snappy_enc(m);
   register_collate(m);
   m.attr("HAS_GPU_KERNELS") = true;
 #else

@@ -153,6 +153,7 @@ class DataFrameWriter(_OptionsMixin):
             num_shards=int(self._options.get("num_shards", 1)),
             engine=self._options.get("engine", "auto"),
             gzip_engine=self._options.get("gzipengine"),
+            snappy_engine=self._options.get("snappyengine"),
         )
 
 

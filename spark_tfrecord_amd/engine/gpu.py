@@ -1780,6 +1780,73 @@ def gzip_image_device(img: torch.Tensor, seg: Optional[int] = None) -> torch.Ten
     return out[:size]
 
 
+def _snap_max_waves(device) -> int:
+    """Resident-wave cap of the Snappy compressor launch, from the kernel's
+    LDS use: a 4-wave block holds four 16 KiB hash tables (66 KiB with the
+    window arrays), so two blocks fit a CU's 160 KiB. More blocks than
+    waves take the kernel's grid-stride loop."""
+    blocks_per_cu = max(1, (160 << 10) // int(_native.SNAP_LDS_BYTES_PER_BLOCK))
+    return (int(_native.SNAP_WAVES_PER_BLOCK) * blocks_per_cu *
+            torch.cuda.get_device_properties(device).multi_processor_count)
+
+
+def snappy_image_device(img: torch.Tensor,
+                        block: Optional[int] = None) -> torch.Tensor:
+    """Uncompressed file image in HBM -> complete `.snappy` file image in
+    HBM, in the layout io/paths.py snappy_walk describes (one raw chunk per
+    block of `block` bytes), via the device compressor
+    (csrc/hip/snappy_enc.hip). Every chunk's place follows from a scan of
+    the chunk lengths on the device, so the only host round trip is one
+    read of the final image size. An empty image is a zero-byte file."""
+    from ..io import paths as P
+
+    check_native()
+    if img.dtype != torch.uint8 or img.dim() != 1 or not img.is_contiguous():
+        raise ValueError(
+            "snappy_image_device expects a contiguous 1-D uint8 tensor")
+    if block is None:
+        block = P.snappy_block_size()
+    block = int(block)
+    if block <= 0:
+        raise ValueError(f"block size must be positive, got {block}")
+    if block > SNAPPY_MAX_CHUNK_RAW:
+        raise ValueError(
+            f"block size {block} is above the device's {SNAPPY_MAX_CHUNK_RAW}"
+            " bytes per chunk")
+    n = img.numel()
+    device = img.device
+    if n == 0:
+        return torch.empty(0, dtype=torch.uint8, device=device)
+    nblk = -(-n // block)
+    slot = (_native.snappy_out_bound(min(block, n)) + 7) & ~7
+    nwaves = min(-(-nblk // 4) * 4, _snap_max_waves(device))
+    staging = torch.empty(nblk * slot, dtype=torch.uint8, device=device)
+    comp_len = torch.empty(nblk, dtype=torch.int64, device=device)
+    comp_off = torch.empty(nblk + 1, dtype=torch.int64, device=device)
+    err = torch.full((1,), -1, dtype=torch.int64, device=device)
+    result = torch.empty(2, dtype=torch.int64, device=device)
+    # no chunk is longer than its block as one literal: n + 10 at the most
+    out_cap = nblk * (8 + 10) + n
+    out = torch.empty(out_cap, dtype=torch.uint8, device=device)
+    _native.gpu_snap_blocks(
+        img.data_ptr(), n, block, nblk, staging.data_ptr(), slot,
+        comp_len.data_ptr(), nwaves, err.data_ptr(), _stream())
+    _excl_sum_into(comp_off.data_ptr(), comp_len.data_ptr(), 1, nblk, device)
+    _native.gpu_snappy_assemble(
+        staging.data_ptr(), slot, comp_len.data_ptr(), comp_off.data_ptr(),
+        n, block, nblk, out.data_ptr(), out_cap, err.data_ptr(),
+        result.data_ptr(), _stream())
+    size, err_word = (int(v) for v in result.tolist())
+    if err_word != -1:
+        raise RuntimeError(
+            f"device snappy compress failed: block {(err_word >> 8) - 1}, "
+            f"cause {err_word & 0xFF}")
+    if size > out_cap:
+        raise RuntimeError(
+            f"device snappy compress: image of {size} bytes, room for {out_cap}")
+    return out[:size]
+
+
 def read_files_to_batch(paths, schema: StructType, record_type: str,
                         verify_crc: bool = True, device="cuda",
                         foreign_gzip: bool = False, sources=None):

@@ -9,6 +9,7 @@ engine (CPU host codec or gfx950 kernels) instead of Catalyst + JVM classes.
 
 from __future__ import annotations
 
+import logging
 import os
 import uuid
 from typing import Dict, List, Optional, Sequence
@@ -27,6 +28,8 @@ from . import paths as P
 __all__ = ["write_tfrecord", "normalize_input"]
 
 RECORD_TYPES = ("Example", "SequenceExample", "ByteArray")
+
+_log = logging.getLogger(__name__)
 
 
 def normalize_input(data, schema: Optional[StructType]) -> pa.Table:
@@ -233,15 +236,55 @@ def _resolve_gzip_engine(gzip_engine: Optional[str], eng: str,
     return val == "device" and codec == "gzip"
 
 
-def _device_image_to_pinned(img, tag: str, gzip_device: bool) -> np.ndarray:
-    """ONE D2H of a device file image into the tag's pinned buffer. With
-    `gzip_device` the image is gzip-compressed in HBM first, so only the
-    compressed bytes cross the host link. Returns the pinned view (valid
-    until the tag's next use)."""
+SNAPPY_ENGINES = ("host", "device")
+
+
+def _resolve_snappy_engine(snappy_engine: Optional[str], eng: str,
+                           codec: Optional[str]) -> bool:
+    """True when snappy output is compressed in HBM (csrc/hip/snappy_enc.hip)
+    instead of by the library on the host. None = the default: "host", or
+    what TFREC_SNAPPY_ENGINE says for GPU-engine writes. For any codec but
+    snappy the choice is ignored. The device takes blocks of up to 1 MiB: a
+    larger TFREC_SNAPPY_BLOCK is compressed on the host, with a log line."""
+    explicit = snappy_engine is not None
+    if not explicit:
+        snappy_engine = (os.environ.get("TFREC_SNAPPY_ENGINE", "host")
+                         if eng == "gpu" else "host")
+    val = str(snappy_engine).lower()
+    if val not in SNAPPY_ENGINES:
+        raise ValueError(
+            f"Unsupported snappy engine {snappy_engine!r} (expected one of "
+            f"{SNAPPY_ENGINES})")
+    if val == "device" and eng != "gpu":
+        raise ValueError(
+            'snappy_engine="device" needs the GPU engine; this write '
+            f"resolved to engine={eng!r}")
+    if val != "device" or codec != "snappy":
+        return False
     from ..engine import gpu as gpu_engine
 
-    if gzip_device:
+    block = P.snappy_block_size()
+    if block > gpu_engine.SNAPPY_MAX_CHUNK_RAW:
+        _log.warning(
+            "snappy_engine=device: TFREC_SNAPPY_BLOCK=%d is above the "
+            "device's %d bytes per chunk; compressing on the host", block,
+            gpu_engine.SNAPPY_MAX_CHUNK_RAW)
+        return False
+    return True
+
+
+def _device_image_to_pinned(img, tag: str,
+                            device_codec: Optional[str]) -> np.ndarray:
+    """ONE D2H of a device file image into the tag's pinned buffer. With
+    `device_codec` ("gzip" or "snappy") the image is compressed in HBM
+    first, so only the compressed bytes cross the host link. Returns the
+    pinned view (valid until the tag's next use)."""
+    from ..engine import gpu as gpu_engine
+
+    if device_codec == "gzip":
         img = gpu_engine.gzip_image_device(img)
+    elif device_codec == "snappy":
+        img = gpu_engine.snappy_image_device(img)
     return gpu_engine.device_to_pinned_view(img, tag=tag)
 
 
@@ -249,7 +292,7 @@ def _encode_and_write(table: pa.Table, schema: StructType, record_type: str,
                       out_dir: str, codec: Optional[str], job_id: str,
                       num_shards: int, shard_offset: int, eng: str,
                       metrics: Optional[IOMetrics] = None,
-                      gzip_device: bool = False):
+                      device_codec: Optional[str] = None):
     """Encode `table` into `num_shards` part files under out_dir. The
     compress+write of shard k runs on a worker thread while shard k+1
     encodes (both the native encoder and zlib release the GIL)."""
@@ -259,8 +302,8 @@ def _encode_and_write(table: pa.Table, schema: StructType, record_type: str,
     bounds = np.linspace(0, R, num_shards + 1).astype(np.int64)
 
     def _compress_write(raw: bytes, fpath: str, rows: int):
-        # with gzip_device, `raw` already is the compressed file image
-        payload = raw if gzip_device else P.compress_bytes(raw, codec)
+        # with device_codec, `raw` already is the compressed file image
+        payload = raw if device_codec else P.compress_bytes(raw, codec)
         P.write_file_atomic(payload, fpath)
         if metrics is not None:
             metrics.add(rows=rows, nbytes=len(payload), files=1)
@@ -280,7 +323,7 @@ def _encode_and_write(table: pa.Table, schema: StructType, record_type: str,
 
             img = gpu_engine.encode_device(
                 gpu_engine.batch_to_device(batch), record_type)
-            raw = _device_image_to_pinned(img, "encw0", gzip_device)
+            raw = _device_image_to_pinned(img, "encw0", device_codec)
         else:
             raw = cpu_engine.encode_batch(batch, record_type)
         _compress_write(raw, fpath, R)
@@ -300,7 +343,7 @@ def _encode_and_write(table: pa.Table, schema: StructType, record_type: str,
 
                 img = gpu_engine.encode_device(
                     gpu_engine.batch_to_device(batch), record_type)
-                raw = _device_image_to_pinned(img, "encw0", gzip_device)
+                raw = _device_image_to_pinned(img, "encw0", device_codec)
             else:
                 raw = cpu_engine.encode_batch(batch, record_type)
             _compress_write(raw, os.path.join(
@@ -334,7 +377,7 @@ def _encode_and_write(table: pa.Table, schema: StructType, record_type: str,
             prev = tag_futs.get(tag)
             if prev is not None:
                 prev.result()  # the tag's pinned buffer is being reused
-            raw = _device_image_to_pinned(img, tag, gzip_device)
+            raw = _device_image_to_pinned(img, tag, device_codec)
         else:
             raw = cpu_engine.encode_batch(batch, record_type)
         f = pool.submit(_compress_write, raw, fpath, hi - lo)
@@ -352,7 +395,8 @@ def write_tfrecord(data, path: str, record_type: str = "Example",
                    engine: str = "auto", write_success: bool = True,
                    shard_offset: int = 0, job_id: Optional[str] = None,
                    _apply_mode: bool = True,
-                   gzip_engine: Optional[str] = None) -> None:
+                   gzip_engine: Optional[str] = None,
+                   snappy_engine: Optional[str] = None) -> None:
     """Write DataFrame-shaped `data` as TFRecord files under `path`.
 
     Fault tolerance: every part file lands via write-to-temp + atomic
@@ -366,7 +410,12 @@ def write_tfrecord(data, path: str, record_type: str = "Example",
     GPU engine compresses gzip output in HBM and copies only the compressed
     image to the host). None takes the default, which TFREC_GZ_ENGINE sets
     for GPU-engine writes. "device" with the CPU engine is an error; with a
-    codec other than gzip it is ignored."""
+    codec other than gzip it is ignored.
+
+    `snappy_engine`: the same choice for the snappy codec ("host" is
+    pyarrow's Snappy, "device" the GPU engine's own compressor); the
+    default comes from TFREC_SNAPPY_ENGINE for GPU-engine writes. A
+    TFREC_SNAPPY_BLOCK above 1 MiB is compressed on the host either way."""
     if record_type not in RECORD_TYPES:
         raise ValueError(
             f"Unsupported recordType {record_type!r} (expected one of {RECORD_TYPES})")
@@ -377,6 +426,10 @@ def write_tfrecord(data, path: str, record_type: str = "Example",
     validate_schema_for_record_type(schema, record_type)
     eng = engine_mod.resolve_engine(engine)
     gzip_device = _resolve_gzip_engine(gzip_engine, eng, codec)
+    snappy_device = _resolve_snappy_engine(snappy_engine, eng, codec)
+    # the codec the GPU engine compresses in HBM, if any
+    device_codec = ("gzip" if gzip_device
+                    else "snappy" if snappy_device else None)
 
     if record_type == "ByteArray":
         # reference: serializeByteArray frames column 0, which must be binary
@@ -423,7 +476,7 @@ def write_tfrecord(data, path: str, record_type: str = "Example",
             # pool (different files page-allocate concurrently; per-file
             # mmap registration would cost ~0.16 ms/MB each on the fresh
             # temp inodes — the r01 config-3 cliff)
-            view = (None if gzip_device
+            view = (None if device_codec
                     else gpu_engine.device_to_pinned_view(img))
 
             def _part_path(p):
@@ -451,7 +504,7 @@ def write_tfrecord(data, path: str, record_type: str = "Example",
                 owner[tuple(_partition_dir_value(v) for v in combos[p])] = p
             ranges = [r for r in ranges if owner[tuple(
                 _partition_dir_value(v) for v in combos[r[0]])] == r[0]]
-            if gzip_device:
+            if device_codec:
                 # each partition's slice of the device image compresses in
                 # HBM; its write overlaps the next partition's compression
                 # (two pinned buffers, as in the multi-shard path)
@@ -461,7 +514,7 @@ def write_tfrecord(data, path: str, record_type: str = "Example",
                     if k >= 2:
                         futs[k - 2].result()  # its pinned buffer is reused
                     payload = _device_image_to_pinned(
-                        img[lo:hi], f"encw{k % 2}", True)
+                        img[lo:hi], f"encw{k % 2}", device_codec)
                     futs.append(pool.submit(_write_payload, payload,
                                             _part_path(p)))
                 sizes = [f.result() for f in futs]
@@ -480,10 +533,10 @@ def write_tfrecord(data, path: str, record_type: str = "Example",
                 sub = stripped.take(pa.array(idxs, type=pa.int64()))
                 _encode_and_write(sub, data_schema, record_type, part_dir(combo),
                                   codec, job_id, num_shards, shard_offset, eng,
-                                  metrics, gzip_device)
+                                  metrics, device_codec)
     else:
         _encode_and_write(table, schema, record_type, path, codec, job_id,
-                          num_shards, shard_offset, eng, metrics, gzip_device)
+                          num_shards, shard_offset, eng, metrics, device_codec)
 
     if write_success:
         P.write_success_marker(path)
