@@ -753,15 +753,27 @@ py::dict scan_stats_debug(py::buffer data, py::array_t<i64> rec_off,
 
 // Host run of the DEFLATE segment inflater core shared with the gfx950
 // kernel (csrc/inflate_core.h): backs CPU tests of the device algorithm.
-py::bytes host_inflate_segment(py::buffer comp, i64 expect) {
+py::bytes host_inflate_segment(py::buffer comp, i64 expect, int lit_bits,
+                               int dist_bits) {
   auto info = comp.request();
+  if (expect < 0) throw std::invalid_argument("host_inflate_segment: expect < 0");
   std::string out(static_cast<size_t>(expect), '\0');
   tfrec::inflate::LaneScratch L;
   uint16_t lit_tab[tfrec::inflate::kLitTabSize];
   uint16_t dist_tab[tfrec::inflate::kDistTabSize];
-  int rc = tfrec::inflate::inflate_one(
-      static_cast<const u8*>(info.ptr), static_cast<i64>(info.size),
-      reinterpret_cast<u8*>(&out[0]), expect, L, lit_tab, dist_tab);
+  const u8* in = static_cast<const u8*>(info.ptr);
+  i64 ilen = static_cast<i64>(info.size * info.itemsize);
+  u8* dst = reinterpret_cast<u8*>(&out[0]);
+  int rc;
+  if (lit_bits == 10 && dist_bits == 8)
+    rc = tfrec::inflate::inflate_one<64, 10, 8>(in, ilen, dst, expect, L,
+                                                lit_tab, dist_tab);
+  else if (lit_bits == 9 && dist_bits == 7)
+    rc = tfrec::inflate::inflate_one<64, 9, 7>(in, ilen, dst, expect, L,
+                                               lit_tab, dist_tab);
+  else
+    throw std::invalid_argument(
+        "host_inflate_segment: root tables are 10/8 or 9/7 bits wide");
   if (rc)
     throw std::runtime_error("inflate_one failed: cause " + std::to_string(rc));
   return py::bytes(out);
@@ -939,8 +951,10 @@ PYBIND11_MODULE(_native, m) {
         [](u32 c1, u32 c2, u64 len2) { return crc32c_combine(c1, c2, len2); },
         "crc(A||B) from crc(A), crc(B), len(B) (GF(2) shift operator)");
   m.def("host_inflate_segment", &host_inflate_segment, py::arg("comp"),
-        py::arg("expect"),
-        "TEST-ONLY: run the device inflater's core on host for one segment");
+        py::arg("expect"), py::arg("lit_bits") = 10, py::arg("dist_bits") = 8,
+        "TEST-ONLY: run the device inflater's core on host for one segment, "
+        "with root tables of 10/8 bits (the whole- and half-wave kernels) or "
+        "9/7 bits (the quarter-wave kernel)");
   m.def("host_inflate_foreign", &host_inflate_foreign, py::arg("gz"),
         py::arg("chunk_bytes"),
         "TEST-ONLY: run the speculative foreign-gzip inflater's core on host "

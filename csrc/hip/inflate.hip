@@ -1,10 +1,11 @@
-// gfx950 DEFLATE inflater: one compressed segment per LANE.
+// gfx950 DEFLATE inflater: one compressed segment per wave, half-wave or
+// quarter-wave.
 //
 // The engine writes gzip as a single member whose deflate stream carries
 // Z_FULL_FLUSH sync points and an FEXTRA table of per-segment extents
 // (spark_tfrecord_amd/io/paths.py compress_bytes). Each segment is an
 // independent raw-deflate sub-stream (dictionary reset at the flush), so
-// inflation parallelizes segment-per-lane with output offsets known up
+// inflation parallelizes across segments with output offsets known up
 // front from the table — one kernel launch inflates a whole batch of files.
 //
 // Huffman decode is inherently bit-serial, so parallelism comes purely from
@@ -45,6 +46,10 @@ namespace {
 
 using tfrec::inflate::LaneScratch;
 using tfrec::inflate::inflate_one;
+
+// Block cap of every launch below; segments past it are reached through the
+// kernels' grid-stride loops (exported as INFLATE_MAX_BLOCKS for the tests).
+constexpr i64 kMaxBlocks = 16384;
 
 // One segment per WAVE: all 64 lanes run the decode in lockstep on the SAME
 // bitstream — every value is wave-uniform (scalarized by the compiler, no
@@ -147,7 +152,7 @@ void gpu_inflate_segments(uintptr_t comp, uintptr_t in_off, uintptr_t in_len,
   if (nseg <= 0) return;
   if (streams_per_wave >= 4) {
     i64 blocks = (nseg + 15) / 16;  // 16 quarter-wave streams per block
-    if (blocks > 16384) blocks = 16384;
+    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
     hipLaunchKernelGGL(inflate_segments_kernel4, dim3((uint32_t)blocks),
                        dim3(256), 0, (hipStream_t)stream, (const u8*)comp,
                        (const i64*)in_off, (const i64*)in_len,
@@ -158,7 +163,7 @@ void gpu_inflate_segments(uintptr_t comp, uintptr_t in_off, uintptr_t in_len,
   }
   if (streams_per_wave <= 1) {
     i64 blocks = (nseg + 3) / 4;  // 4 waves (segments) per block
-    if (blocks > 16384) blocks = 16384;
+    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
     hipLaunchKernelGGL(inflate_segments_kernel1, dim3((uint32_t)blocks),
                        dim3(256), 0, (hipStream_t)stream, (const u8*)comp,
                        (const i64*)in_off, (const i64*)in_len,
@@ -168,7 +173,7 @@ void gpu_inflate_segments(uintptr_t comp, uintptr_t in_off, uintptr_t in_len,
     return;
   }
   i64 blocks = (nseg + 7) / 8;  // 8 half-wave streams per block
-  if (blocks > 16384) blocks = 16384;
+  if (blocks > kMaxBlocks) blocks = kMaxBlocks;
   hipLaunchKernelGGL(inflate_segments_kernel, dim3((uint32_t)blocks), dim3(256),
                      0, (hipStream_t)stream, (const u8*)comp,
                      (const i64*)in_off, (const i64*)in_len,
@@ -180,11 +185,12 @@ void gpu_inflate_segments(uintptr_t comp, uintptr_t in_off, uintptr_t in_len,
 }  // namespace
 
 void register_inflate(py::module_& m) {
+  m.attr("INFLATE_MAX_BLOCKS") = kMaxBlocks;
   m.def("gpu_inflate_segments", &gpu_inflate_segments, py::arg("comp"),
         py::arg("in_off"), py::arg("in_len"), py::arg("out_off"),
         py::arg("out_len"), py::arg("nseg"), py::arg("out"), py::arg("err"),
         py::arg("stream"), py::arg("streams_per_wave") = 1,
         "Inflate full-flush deflate segments (1 = one per wave, 2 = one per "
-        "half-wave); err[0] (init ~0ull) collects ((seg+1)<<8)|cause of the "
-        "first failure");
+        "half-wave, 4 = one per quarter-wave); err[0] (init ~0ull) collects "
+        "((seg+1)<<8)|cause of the first failure");
 }

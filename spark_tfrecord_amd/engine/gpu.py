@@ -1284,8 +1284,9 @@ def gz_device_meta(path: str):
 
 
 def _device_inflate_group(data: torch.Tensor, gz_items, device) -> bool:
-    """Inflate several gzip files' full-flush segments in ONE kernel launch
-    (one segment per lane, csrc/hip/inflate.hip), each file's output landing
+    """Inflate several gzip files' full-flush segments in one kernel launch
+    per kernel shape (one segment per wave or per half-wave,
+    csrc/hip/inflate.hip), each file's output landing
     at its slice of `data`. gz_items = [(path, parse_gz_segments_file meta,
     out_base)]. Compressed bodies DMA straight from the page cache (pinned
     mmaps). Returns False when the kernel reported any malformed segment —

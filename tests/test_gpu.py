@@ -605,9 +605,11 @@ class TestWaveProtoPath:
 
 
 class TestDeviceInflate:
-    """csrc/hip/inflate.hip: one-segment-per-lane DEFLATE decode of our
-    segment-table gzip. Numerics vs host zlib; stored/fixed/dynamic blocks;
-    foreign-gzip and corrupt-stream fallbacks."""
+    """csrc/hip/inflate.hip: one-segment-per-wave (or half-wave) DEFLATE
+    decode of our segment-table gzip. Numerics vs host zlib on zlib-made
+    data; stored/fixed/dynamic blocks; foreign-gzip and corrupt-stream
+    fallbacks. Hand-built streams and forced kernel shapes:
+    tests/test_gpu_inflate.py."""
 
     def _gz_file(self, tmp_path, data, name="t.tfrecord.gz"):
         from spark_tfrecord_amd.io import paths as P

@@ -1,11 +1,13 @@
 """CPU tests of the device DEFLATE inflater core (csrc/inflate_core.h).
 
-The exact code that runs one-segment-per-lane on the GPU also compiles for
+The exact code that runs one-segment-per-wave on the GPU also compiles for
 the host (`_native.host_inflate_segment`), so the algorithm is fully
 testable here: numerics vs zlib across entropy profiles, block-type
 coverage (stored / fixed / dynamic), malformed-stream rejection, and the
 regression for the prefetch-refill underflow (a nearly-empty prefetch
-register delivered <16 bits to a 16-bit read at segment tails)."""
+register delivered <16 bits to a 16-bit read at segment tails). The host
+build takes the serial copy and table-fill paths; the lane-split ones are
+covered by csrc/tests/inflate_selftest.cpp and tests/test_gpu_inflate.py."""
 
 import gzip
 import zlib
@@ -13,6 +15,7 @@ import zlib
 import numpy as np
 import pytest
 
+import inflate_cases as C
 from spark_tfrecord_amd import _native
 from spark_tfrecord_amd.io import paths as P
 
@@ -161,3 +164,60 @@ class TestRootTableEdges:
             except RuntimeError:
                 pass
             seg[i] ^= bit
+
+
+WIDTHS = [(10, 8), (9, 7)]  # whole-/half-wave kernels, quarter-wave kernel
+VALID = C.valid_segments()
+MALFORMED = C.malformed_segments()
+
+
+class TestHandBuiltSegments:
+    """tests/inflate_cases.py through the host build of the core, at the
+    root-table widths of every device instantiation: the serial half of
+    what tests/test_gpu_inflate.py asks of the kernels."""
+
+    @pytest.mark.parametrize("lit_bits,dist_bits", WIDTHS)
+    def test_valid_segments_match_zlib(self, lit_bits, dist_bits):
+        for name, comp, want in VALID:
+            got = _native.host_inflate_segment(comp, len(want), lit_bits,
+                                               dist_bits)
+            assert got == want, name
+
+    def test_default_widths_are_10_and_8(self):
+        name, comp, want = VALID[0]
+        assert _native.host_inflate_segment(comp, len(want)) == want
+        with pytest.raises(ValueError):
+            _native.host_inflate_segment(comp, len(want), 11, 8)
+
+    def test_long_code_block_misses_the_root_tables(self):
+        """The case set's long-code block has lit/len and distance codes of
+        every length 1..15, so both table widths fall through to the compare
+        chain, and the 10-bit literal and 8-bit distance do so at 9/7 only."""
+        assert sorted(C.LONG_LIT.values()) == list(range(1, 16)) + [15]
+        assert sorted(C.LONG_DIST.values()) == list(range(1, 16)) + [15]
+        assert C.LONG_LIT[ord("g")] == 10 and C.LONG_DIST[4] == 8
+        geo = dict((n, w) for n, _, w in VALID)["long_geometry_final"]
+        assert b"g" in geo and b"\xff" in geo and len(geo) > 40_000
+
+    @pytest.mark.parametrize("name,comp,expect,cause", MALFORMED,
+                             ids=[m[0] for m in MALFORMED])
+    def test_malformed_segment_is_refused(self, name, comp, expect, cause):
+        got = [C.host_cause(comp, expect, lb, db) for lb, db in WIDTHS]
+        assert got[0] != 0 and got[0] == got[1]
+        if cause is not None:
+            assert got[0] == cause
+
+    def test_every_cause_code_is_reached(self):
+        assert {m[3] for m in MALFORMED} >= set(range(1, 18))
+
+    def test_gz_file_helper_writes_the_library_layout(self):
+        by_name = {n: (c, w) for n, c, w in VALID}
+        segs = [by_name["long_geometry_sync"], by_name["fixed_literals_sync"],
+                by_name["stored_65535"]]
+        gz, data = C.gz_file(segs)
+        body_off, table, crc, isize = P.parse_gz_segments(gz)
+        assert table == [(len(c), len(w)) for c, w in segs]
+        assert isize == len(data) and crc == zlib.crc32(data)
+        assert gzip.decompress(gz) == data == P._gunzip_parallel(gz)
+        ours = P.compress_bytes(b"", "gzip")
+        assert C.gz_file([by_name["empty_as_zlib_writes_it"]])[0] == ours
