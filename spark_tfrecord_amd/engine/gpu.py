@@ -807,15 +807,14 @@ def write_batch_to_file(batch: RecordBatch, path: str,
     err = torch.zeros(2, dtype=torch.int32, device=device)
     ptr, pinned = _native.file_mmap_pinned(path, total, True)
     if not pinned:
-        _native.gpu_emit_records(cols_dev.data_ptr(), blob.data_ptr(),
-                                 FMT[record_type], 0, R, frame_off.data_ptr(),
-                                 file.data_ptr(), err.data_ptr(), _stream(),
-                                 total // R)
-        _check_emit_err(err)
-        _write_file_staged(file, path)
-        return total
+        # The mapping cannot be registered: the slices land in a pinned
+        # staging buffer of the file's size instead and are written out from
+        # there as they arrive. No copy of an earlier call is still in
+        # flight into the buffer: every call ends with its copies landed.
+        ptr = pinned_buffer("fwrite_slices", total).data_ptr()
     main = torch.cuda.current_stream()
     streams = _dma_streams()
+    landed = []  # (event, b0, b1) per non-empty slice
     for s in range(S):
         _native.gpu_emit_records(cols_dev.data_ptr(), blob.data_ptr(),
                                  FMT[record_type], ridx[s], ridx[s + 1],
@@ -827,15 +826,40 @@ def write_batch_to_file(batch: RecordBatch, path: str,
             w.wait_stream(main)
             _native.gpu_memcpy_d2h(ptr + b0, file.data_ptr() + b0, b1 - b0,
                                    w.cuda_stream)
-    for w in streams:
-        w.synchronize()
-    if _SYNC_WRITES:
-        _native.file_mmap_sync(path)
+            if not pinned:
+                ev = torch.cuda.Event()
+                ev.record(w)
+                landed.append((ev, b0, b1))
+    if pinned:
+        for w in streams:
+            w.synchronize()
+        if _SYNC_WRITES:
+            _native.file_mmap_sync(path)
+    else:
+        _write_staged_slices(path, ptr, landed, total)
     _check_emit_err(err)
     return total
 
 
-# what the last read_file_to_batch_pipelined call on a registered mapping did:
+def _write_staged_slices(path: str, ptr: int, landed, total: int):
+    """The file-side half of a sliced write through pinned staging at `ptr`:
+    each slice [b0, b1) is written once its D2H copy (event) has landed, while
+    the later slices are still being emitted and copied."""
+    fd = os.open(path, os.O_RDWR | os.O_CREAT, 0o644)
+    try:
+        for ev, b0, b1 in landed:
+            ev.synchronize()
+            _native.pwrite_parallel(fd, ptr + b0, b1 - b0, b0)
+        os.ftruncate(fd, total)
+        if _SYNC_WRITES:
+            os.fsync(fd)
+    finally:
+        os.close(fd)
+        for w in _dma_streams():  # also when a write failed midway
+            w.synchronize()
+
+
+# what the last read_file_to_batch_pipelined call on a non-empty file did:
 # path = "streamed" | "fallback" (streamed attempt abandoned) | "unstreamed"
 # (TFREC_STREAM_DECODE=0), the slice count, the buffer regrows and how often
 # the streamed path blocked on the device (host_waits)
@@ -1154,34 +1178,47 @@ class _StreamedRead:
         return RecordBatch(self.schema, cols, R)
 
 
-def _issue_h2d_slices(data: torch.Tensor, ptr: int, plan) -> list:
-    """Issue ALL H2D slices up front on the side streams. Returns one list
-    of events per slice: the main stream gates each slice's work on just
-    that slice's copies."""
-    main = torch.cuda.current_stream()
-    streams = _dma_streams()
-    for st in streams:
-        st.wait_stream(main)  # `data` allocation ordering
-    events = []
-    for s, p in enumerate(plan):
-        # each slice goes half on either DMA stream: the streams share the
-        # link, so whole slices alternating between them land in PAIRS;
-        # split, slice k lands alone while k+1 is still in flight
-        half = (p.b1 - p.b0) // 2 if _SPLIT_SLICES and len(streams) > 1 else 0
-        parts = ([(p.b0, p.b0 + half, 0), (p.b0 + half, p.b1, 1)] if half
-                 else [(p.b0, p.b1, s % len(streams))])
-        evs = []
-        for lo, hi, k in parts:
-            st = streams[k]
-            _native.gpu_memcpy_h2d(data.data_ptr() + lo, ptr + lo, hi - lo,
-                                   st.cuda_stream)
-            ev = torch.cuda.Event()
-            ev.record(st)
-            evs.append(ev)
-        events.append(evs)
-    for st in streams:
-        data.record_stream(st)
-    return events
+class _SliceCopies:
+    """The H2D slices of one read on the side streams. `events` holds one
+    list of events per issued slice: the main stream gates each slice's work
+    on just that slice's copies. `ptr` is the file's registered mapping, or,
+    with `fd`, a pinned staging buffer of the file's size for a file whose
+    mapping cannot be registered: issue() then reads each slice from the
+    file into the buffer before it copies it."""
+
+    def __init__(self, data: torch.Tensor, plan, ptr: int,
+                 fd: Optional[int] = None):
+        self.data, self.plan, self.ptr, self.fd = data, plan, ptr, fd
+        self.events = []
+        main = torch.cuda.current_stream()
+        for st in _dma_streams():
+            st.wait_stream(main)  # `data` allocation ordering
+            data.record_stream(st)
+
+    def issue(self, upto: int):
+        """Issue the slices below `upto` that are not yet under way."""
+        streams = _dma_streams()
+        for s in range(len(self.events), min(upto, len(self.plan))):
+            p = self.plan[s]
+            if self.fd is not None:
+                _native.pread_parallel(self.fd, self.ptr + p.b0, p.b1 - p.b0,
+                                       p.b0)
+            # each slice goes half on either DMA stream: the streams share
+            # the link, so whole slices alternating between them land in
+            # PAIRS; split, slice k lands alone while k+1 is still in flight
+            half = ((p.b1 - p.b0) // 2
+                    if _SPLIT_SLICES and len(streams) > 1 else 0)
+            parts = ([(p.b0, p.b0 + half, 0), (p.b0 + half, p.b1, 1)] if half
+                     else [(p.b0, p.b1, s % len(streams))])
+            evs = []
+            for lo, hi, k in parts:
+                st = streams[k]
+                _native.gpu_memcpy_h2d(self.data.data_ptr() + lo,
+                                       self.ptr + lo, hi - lo, st.cuda_stream)
+                ev = torch.cuda.Event()
+                ev.record(st)
+                evs.append(ev)
+            self.events.append(evs)
 
 
 def _scan_blocks(p: stream_plan.SlicePlan) -> int:
@@ -1205,16 +1242,17 @@ def _count_slice(data, p, evs, block_counts, base: int) -> int:
     return nb
 
 
-def _read_unstreamed(data, plan, block_counts, events, first: int,
-                     schema: StructType, record_type: str,
+def _read_unstreamed(data, plan, block_counts, copies: _SliceCopies,
+                     first: int, schema: StructType, record_type: str,
                      verify_crc: bool) -> RecordBatch:
     """The unstreamed read: COUNT under the DMA for the slices from `first`
     on (the earlier ones have been counted), then the whole-file
     _emit_and_chain + decode_device. TFREC_STREAM_DECODE=0 starts here with
     first == 0; the streamed loop leaves through here on a broken chain."""
     last_read["path"] = "fallback" if _STREAM_DECODE else "unstreamed"
+    copies.issue(len(plan))
     base = sum(_scan_blocks(p) for p in plan[:first])
-    for p, evs in zip(plan[first:], events[first:]):
+    for p, evs in zip(plan[first:], copies.events[first:]):
         base += _count_slice(data, p, evs, block_counts, base)
     ranges = [(p.scan_lo, p.scan_hi) for p in plan if p.scan_hi > p.scan_lo]
     off, lens, _ = _emit_and_chain(data, ranges, block_counts, data.numel())
@@ -1233,7 +1271,10 @@ def read_file_to_batch_pipelined(path: str, schema: StructType, record_type: str
     slice's launch (their load window extends past the boundary). After the
     last slice only that slice's work remains. A broken frame chain abandons
     the streamed attempt for _read_unstreamed, which is also what
-    TFREC_STREAM_DECODE=0 runs."""
+    TFREC_STREAM_DECODE=0 runs. The slices come from the file's registered
+    mapping, all issued up front. Where the mapping cannot be registered
+    they come through pinned staging, each one read from the file while its
+    predecessor is copied and the one before that is decoded."""
     check_native()
     n = os.path.getsize(path)
     if n == 0:
@@ -1241,20 +1282,34 @@ def read_file_to_batch_pipelined(path: str, schema: StructType, record_type: str
         return decode_device(torch.zeros(0, dtype=torch.uint8, device=device),
                              z, z.clone(), schema, record_type, verify_crc)
     ptr, pinned = _native.file_mmap_pinned(path, n, False)
-    if not pinned:
-        data = _read_file_staged(path, torch.empty(n, dtype=torch.uint8,
-                                                   device=device))
-        off, lens = scan_frames_device(data)
-        return decode_device(data, off, lens, schema, record_type, verify_crc)
+    if pinned:
+        return _read_sliced(n, ptr, None, schema, record_type, verify_crc,
+                            device)
+    for st in _dma_streams():
+        st.synchronize()  # an earlier read's copies out of the staging buffer
+    stage = pinned_buffer("fread_slices", n)
+    fd = os.open(path, os.O_RDONLY)
+    try:
+        return _read_sliced(n, stage.data_ptr(), fd, schema, record_type,
+                            verify_crc, device)
+    finally:
+        os.close(fd)
+
+
+def _read_sliced(n: int, ptr: int, fd: Optional[int], schema: StructType,
+                 record_type: str, verify_crc: bool, device) -> RecordBatch:
+    """read_file_to_batch_pipelined over the n bytes at `ptr` (fd is None),
+    or over those of file `fd` staged through the pinned buffer at `ptr`."""
     data = torch.empty(n, dtype=torch.uint8, device=device)
     plan = stream_plan.plan_slices(n, _READ_SLICE)
     S = len(plan)
     # pre-size the per-block count buffer over the slice scan ranges
     block_counts = torch.empty(max(sum(_scan_blocks(p) for p in plan), 1),
                                dtype=torch.int64, device=data.device)
-    events = _issue_h2d_slices(data, ptr, plan)
+    copies = _SliceCopies(data, plan, ptr, fd)
+    copies.issue(S if fd is None else 1)
     last_read.update(path="streamed", slices=S, regrows=0, host_waits=0)
-    unstreamed = (data, plan, block_counts, events)
+    unstreamed = (data, plan, block_counts, copies)
     decode = (schema, record_type, verify_crc)
     if not _STREAM_DECODE:
         return _read_unstreamed(*unstreamed, 0, *decode)
@@ -1262,7 +1317,10 @@ def read_file_to_batch_pipelined(path: str, schema: StructType, record_type: str
     rd = _StreamedRead(data, S, *decode)
     base = 0  # block_counts offset of the current slice
     for s, p in enumerate(plan):
-        nb = _count_slice(data, p, events[s], block_counts, base)
+        nb = _count_slice(data, p, copies.events[s], block_counts, base)
+        # staged: the host reads slice s + 1 here, under slice s's copy and
+        # COUNT and slice s - 1's kernels, before step() blocks on them
+        copies.issue(s + 2)
         counts = block_counts[base:base + nb] if nb else None
         base += nb
         if not rd.step(p, counts, last=s == S - 1):

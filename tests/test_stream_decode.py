@@ -125,13 +125,12 @@ def _oracle(img, schema, record_type, verify_crc):
 
 def _streamed(tmp_path, monkeypatch, img, schema, record_type, verify_crc,
               read_slice, extract=True):
-    from spark_tfrecord_amd import _native
+    # the slices come from the file's registered mapping, or through pinned
+    # staging where the platform registers none (forced further below)
     g = _g()
     path = str(tmp_path / "f.tfrecord")
     with open(path, "wb") as f:
         f.write(img)
-    if img:  # the streamed reader needs the registered mapping
-        assert _native.file_mmap_pinned(path, len(img), False)[1]
     monkeypatch.setattr(g, "_STREAM_DECODE", True)
     monkeypatch.setattr(g, "_STREAM_EXTRACT", extract)
     if read_slice:
@@ -443,16 +442,80 @@ def test_false_positive_header_falls_back(tmp_path, monkeypatch, verify_crc,
     # file is three 4 KiB slices long and record `at` puts the fake header in
     # the first, the middle and the last of them: the streamed loop leaves
     # for the fallback from its first slice, mid-loop and at the end.
-    from spark_tfrecord_amd import _native
-    head = struct.pack("<Q", 5)
-    fake = head + struct.pack("<I", _native.masked_crc32c(head)) + b"y" * 40
-    schema = stf.StructType([stf.StructField("b", stf.BinaryType(), True)])
-    vals = [b"z" * (i % 50) for i in range(200)]
-    vals[at] = fake
-    img = cpu_engine.encode_batch(_batch(schema, {"b": vals}), "Example")
+    img, schema = _false_positive_file(at)
     off, _ = _frame_bounds(img)
     assert len(img) > 2 * 4096 and len(img) <= 3 * 4096
     assert int(off[at]) // 4096 == {2: 0, 120: 1, 199: 2}[at]
     want = _check(tmp_path, monkeypatch, (img, schema, "Example"), 4 << 10,
                   verify_crc, extract, path="fallback")
     assert want.num_rows == 200
+
+
+def _false_positive_file(at):
+    from spark_tfrecord_amd import _native
+    head = struct.pack("<Q", 5)
+    fake = head + struct.pack("<I", _native.masked_crc32c(head)) + b"y" * 40
+    schema = stf.StructType([stf.StructField("b", stf.BinaryType(), True)])
+    vals = [b"z" * (i % 50) for i in range(200)]
+    vals[at] = fake
+    return cpu_engine.encode_batch(_batch(schema, {"b": vals}), "Example"), schema
+
+
+# ---------------------------------------------------------------------------
+# A platform that registers no mapping: the same reads and the sliced write
+# through pinned staging
+# ---------------------------------------------------------------------------
+
+def _register_nothing(monkeypatch):
+    from spark_tfrecord_amd import _native
+    monkeypatch.setattr(_native, "file_mmap_pinned",
+                        lambda path, n, writable: (0, False))
+
+
+@ext
+def test_unregistered_mapping_streams_through_staging(tmp_path, monkeypatch,
+                                                      extract):
+    _register_nothing(monkeypatch)
+    g = _g()
+    want = _check(tmp_path, monkeypatch, _flagship(), 2 << 10, True, extract,
+                  min_slices=21)
+    assert want.num_rows == 300
+    assert g.last_read["host_waits"] <= g.last_read["slices"] + 3
+    # again: the staging buffer is reused, now with a file of another size
+    _check(tmp_path, monkeypatch, _ragged(), 8 << 10, True, extract,
+           min_slices=4)
+
+
+@pytest.mark.parametrize("stream", [True, False])
+def test_unregistered_mapping_unstreamed_paths(tmp_path, monkeypatch, stream):
+    # the fallback leaves the loop at the first slice, the forced unstreamed
+    # read never enters it: the slices not yet staged are issued there
+    _register_nothing(monkeypatch)
+    g = _g()
+    img, schema = _false_positive_file(2)
+    want = _oracle(img, schema, "Example", True)
+    path = str(tmp_path / "u.tfrecord")
+    with open(path, "wb") as f:
+        f.write(img)
+    monkeypatch.setattr(g, "_STREAM_DECODE", stream)
+    monkeypatch.setattr(g, "_READ_SLICE", 4 << 10)
+    g.last_read.clear()
+    _assert_same(g.read_file_to_batch_pipelined(path, schema, "Example"), want)
+    assert g.last_read["path"] == ("fallback" if stream else "unstreamed")
+    assert g.last_read["slices"] == 3
+
+
+@pytest.mark.parametrize("slices", [1, 5])
+def test_unregistered_mapping_sliced_write(tmp_path, monkeypatch, slices):
+    from bench import make_batch
+    _register_nothing(monkeypatch)
+    g = _g()
+    b = make_batch(300, seed=5)
+    want = cpu_engine.encode_batch(b, "Example")
+    path = str(tmp_path / "w.tfrecord")
+    with open(path, "wb") as f:  # a longer file is there already
+        f.write(b"\xa5" * (len(want) + 100))
+    dev = g.batch_to_device(b)
+    assert g.write_batch_to_file(dev, path, "Example", slices=slices) == len(want)
+    with open(path, "rb") as f:
+        assert f.read() == want
