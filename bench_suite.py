@@ -587,6 +587,43 @@ def _torch_collate(batch, lo, hi, torch):
     return out
 
 
+def _torch_ragged(batch, lo, hi, torch):
+    """The packed spec (id / ints / floats Ragged, tokens Ragged2D) for rows
+    [lo, hi) of one decoded shard in torch ops: per level a cumsum of the
+    counts, a repeat_interleave (which sizes its output on the host) and an
+    index. Exact-size outputs: the comparison for the ragged kernels' values
+    up to the batch's total and their offsets."""
+    dev = batch.column("id").values.device
+
+    def level(src_off, first, n):
+        """n consecutive entries of src_off from `first` (a tensor or int)
+        -> (batch offsets [n+1], source index of every child)."""
+        start = src_off[first:first + n] if isinstance(first, int) \
+            else src_off[first]
+        cnt = (src_off[first + 1:first + n + 1] if isinstance(first, int)
+               else src_off[first + 1]) - start
+        off = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        off[1:] = cnt.cumsum(0)
+        owner = torch.repeat_interleave(cnt)
+        child = start[owner] + torch.arange(owner.numel(), device=dev) \
+            - off[owner]
+        return off, child
+
+    out = {}
+    for name in ("id", "ints", "floats"):
+        col = batch.column(name)
+        off, idx = level(col.row_off, lo, hi - lo)
+        out[name] = col.values[idx]
+        out[name + "_offsets"] = off.int()
+    tokens = batch.column("tokens")
+    ioff, item = level(tokens.row_off, lo, hi - lo)
+    voff, idx = level(tokens.elem_off, item, item.numel())
+    out["tokens"] = tokens.values[idx]
+    out["tokens_item_offsets"] = voff.int()
+    out["tokens_offsets"] = ioff.int()
+    return out
+
+
 def bench_collate(args):
     """--rows flagship Example rows in 8 shards, batches of 8192. Whole
     pipelines, alternating after a warm-up of each: (a) the ragged
@@ -594,8 +631,10 @@ def bench_collate(args):
     (c) the same with shuffle_window=4, (c4) that with prefetch=4. Collation
     alone over one decoded
     shard: (k) collate_rows_kernel through Collator.run, (d) the same four
-    columns in torch indexing ops. --collate-part kernel|torch runs only
-    (k) or (d), for a kernel trace of its own; none only decodes the shard."""
+    columns in torch indexing ops, (rk) the four columns packed (Ragged /
+    Ragged2D) through Collator.run, (rd) those in torch ops. --collate-part
+    kernel|torch|ragged|ragged_torch runs only that loop, for a kernel trace
+    of its own; none only decodes the shard."""
     import torch
 
     import spark_tfrecord_amd as stf
@@ -603,6 +642,7 @@ def bench_collate(args):
     from spark_tfrecord_amd.engine import gpu as gpu_engine
     from spark_tfrecord_amd.io import paths as P
     from spark_tfrecord_amd.torch_data import (FixedLen, Padded, Padded2D,
+                                               Ragged, Ragged2D,
                                                TFRecordBatchDataset,
                                                TFRecordIterableDataset)
 
@@ -614,7 +654,8 @@ def bench_collate(args):
     out = os.path.join(d, "t")
     stf.write_tfrecord(_flagship_table(rows, 9 + rank), out,
                        record_type="Example", num_shards=8, engine="gpu")
-    schema = stf.read_tfrecord(out, engine="gpu").schema
+    # every shard has the same columns: one is enough for the schema
+    schema = stf.read_tfrecord(P.list_data_files(out)[0], engine="gpu").schema
     spec = {"id": FixedLen(), "ints": Padded(8), "floats": FixedLen(16),
             "tokens": Padded2D(2, 12)}
     part = args.collate_part
@@ -641,13 +682,42 @@ def bench_collate(args):
         assert not bool(outs["_bad"])  # the one wait, as the kernel's
         return outs
 
-    alone = {"kernel": run_kernel, "torch": run_torch}
-    if part in ("kernel", "torch", "none"):
+    # the same columns packed; capacities as the padded shapes, so the
+    # bytes written differ by the offsets against the length words only
+    spec_r = {"id": Ragged(capacity=B), "ints": Ragged(capacity=8 * B),
+              "floats": Ragged(capacity=16 * B),
+              "tokens": Ragged2D(2 * B, 24 * B)}
+    co_r = Collator(schema, spec_r, "gpu")
+    co_r.set_window([shard])
+
+    def run_ragged():
+        for slot, row in sels:
+            outs, status = co_r.run(slot, row)
+        assert status[0] == (1 << 64) - 1
+        return outs
+
+    def run_ragged_torch():
+        for lo, hi in ranges:
+            outs = _torch_ragged(shard, lo, hi, torch)
+        return outs
+
+    alone = {"kernel": run_kernel, "torch": run_torch,
+             "ragged": run_ragged, "ragged_torch": run_ragged_torch}
+    if part != "all":
         alone = {k: f for k, f in alone.items() if k == part}
     if part == "all":
         a, b = run_kernel(), run_torch()
         for k in a:  # the two collations agree
             assert torch.equal(a[k], b[k]), k
+        a, b = run_ragged(), run_ragged_torch()
+        for k in b:  # and the packed ones, up to the batch's totals
+            assert torch.equal(a[k][:b[k].numel()], b[k]), k
+
+    colls = {"kernel": co, "ragged": co_r}
+
+    def nbytes(outs):
+        return sum(t.numel() * t.element_size() for k, t in outs.items()
+                   if not k.startswith("_"))
     el_alone = dict.fromkeys(alone, 0.0)
     for f in alone.values():
         f()  # warm-up
@@ -664,6 +734,10 @@ def bench_collate(args):
                          "reps": args.reps, "part": k,
                          "ms_per_batch": round(
                              t * 1e3 / (args.reps * len(ranges)), 4),
+                         "out_bytes_last_batch": nbytes(alone[k]()),
+                         "launches_per_batch":
+                             colls[k].launches / colls[k].host_waits
+                             if k in colls else None,
                          "engine": "gpu"}, t, 1)
     if part != "all":
         shutil.rmtree(d, ignore_errors=True)
@@ -734,7 +808,8 @@ def main():
     ap.add_argument("--rows", type=int, default=1_000_000)
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--collate-part", default="all",
-                    choices=["all", "kernel", "torch", "none"],
+                    choices=["all", "kernel", "torch", "ragged",
+                             "ragged_torch", "none"],
                     help="collate: run only one collation-alone loop "
                          "(for a kernel trace of its own)")
     args = ap.parse_args()

@@ -1,5 +1,5 @@
 // Batch collation core, shared host/device: gathers ragged rows of several
-// decoded shards into padded dense tensors.
+// decoded shards into padded dense tensors, or into packed values + offsets.
 //
 // A batch row is a (slot, row) pair into a window of decoded shards. Every
 // output column is a flat array of B*T*L elements (FixedLen: T = 1, L = K;
@@ -22,6 +22,25 @@
 //             item's elements against L; a row is truncated once
 // The two PADDED2D sources differ only in which offset arrays are walked
 // (list_off/sub_off or row_off/elem_off) and in the element size.
+//
+// The packed modes keep the wire form's shape, re-based to the batch:
+//   RAGGED    the rows' values back to back in `cap` elements, offsets[B+1];
+//             a row is cut to its first L values (counted as truncated)
+//   RAGGED2D  the rows' items (lists or strings) back to back: values in
+//             `cap` elements, item_offsets[icap+1], offsets[B+1] over items
+// They run in two steps. Step one gives every row its raw 64-bit offsets in
+// batch order (row_counts + a prefix sum: serial on the host, a block scan on
+// the device) and ragged_row() writes them, the clamped int32 offsets, and
+// raises CAPACITY at the first row whose end passes a capacity. Step two cuts
+// the capacity into units like the dense columns; ragged_value_unit() and
+// ragged_item_unit() produce one unit from the RowRef of the batch row its
+// first position lies in (the caller finds that row: a cursor on the host, a
+// map staged in LDS on the device). Offsets are min(raw, capacity), values
+// past the batch's total are zero, item offsets past the last item repeat
+// the total: every output byte is defined, on errors too.
+//
+// osize 4 on an 8-byte column narrows int64 to int32 in the store; a copied
+// value outside int32 raises RANGE and its low 32 bits are stored.
 #pragma once
 
 #include <cstdint>
@@ -38,15 +57,27 @@ using u32 = uint32_t;
 using u64 = uint64_t;
 using u8 = uint8_t;
 
-enum Mode : int { CM_FIXED = 0, CM_PADDED = 1, CM_PADDED2D = 2 };
+enum Mode : int {
+  CM_FIXED = 0,
+  CM_PADDED = 1,
+  CM_PADDED2D = 2,
+  CM_RAGGED = 3,
+  CM_RAGGED2D = 4,
+};
 
 // Cause codes (the low byte of the status word).
-enum Cause : int { CC_OK = 0, CC_MISSING = 1, CC_LENGTH = 2 };
+enum Cause : int {
+  CC_OK = 0,
+  CC_MISSING = 1,
+  CC_LENGTH = 2,
+  CC_RANGE = 3,     // an int64 value does not fit the int32 output
+  CC_CAPACITY = 4,  // RAGGED*: the batch's total passes a capacity
+};
 
 enum Flags : int {
   CF_DEFAULT = 1,   // FIXED: `fill` is a default for absent/empty rows
-  CF_TRUNCATE = 2,  // PADDED*: over-long rows are cut and counted
-  CF_BYTES = 4,     // PADDED2D: walk row_off/elem_off (else list_off/sub_off)
+  CF_TRUNCATE = 2,  // PADDED*, RAGGED: over-long rows are cut and counted
+  CF_BYTES = 4,     // *2D: walk row_off/elem_off (else list_off/sub_off)
 };
 
 // The six wire-form pointers of one column of one window slot
@@ -61,22 +92,29 @@ struct Src {
 };
 constexpr int kSrcWords = 6;
 
-// One output column; twelve 8-byte words, built by collate.py.
+// One output column; sixteen 8-byte words, built by collate.py. The dense
+// kernel and the ragged gather kernel each walk their own tile prefix (tile0,
+// rtile0); a column has no tiles in the other kernel's.
 struct Col {
   i64 mode;
-  i64 esize;  // 8, 4 or 1
+  i64 esize;  // source element: 8, 4 or 1
   i64 T;      // 1 unless PADDED2D
-  i64 L;      // K for FIXED
+  i64 L;      // K for FIXED; RAGGED: max_len (huge when there is none)
   u64 fill;   // pad or default bits, in the low esize bytes
   i64 flags;
-  u8* out;     // B*T*L elements
-  i32* len;    // PADDED: [B]; PADDED2D: [B, T]; FIXED: null
-  i32* outer;  // PADDED2D: [B]; else null
-  i64 tile0;   // first tile of this column (the kernel's prefix table)
+  u8* out;     // dense: B*T*L elements; RAGGED*: cap elements
+  i32* len;    // PADDED: [B]; PADDED2D: [B, T]; RAGGED*: offsets [B+1]
+  i32* outer;  // PADDED2D: [B]; RAGGED2D: item_offsets [icap+1]; else null
+  i64 tile0;   // first tile of this column in the dense kernel
   i64 units;   // units in this column
-  i64 rsv;
+  i64 osize;   // output element: 0 or esize, or 4 when int64 narrows to int32
+  i64* raw;    // RAGGED*: scratch, raw value offsets [B+1], then (RAGGED2D)
+               // raw item offsets [B+1]
+  i64 cap;     // RAGGED*: value capacity
+  i64 icap;    // RAGGED2D: item capacity
+  i64 rtile0;  // first tile of this column in the ragged gather kernel
 };
-constexpr int kColWords = 12;
+constexpr int kColWords = 16;
 constexpr int kMaxCols = 64;
 constexpr int kTileUnits = 1024;  // units per tile (256 lanes x 4)
 
@@ -105,6 +143,16 @@ struct RowWords {
   int cause;
   bool truncated;
 };
+
+// int64 values are stored as int32. osize was a reserved zero word once: a
+// descriptor that leaves it 0 stores esize bytes, as before.
+TFR_HOSTDEV inline bool narrows(const Col& col) {
+  return col.esize == 8 && col.osize == 4;
+}
+
+TFR_HOSTDEV inline bool is_ragged(const Col& col) {
+  return col.mode >= CM_RAGGED;
+}
 
 TFR_HOSTDEV inline const Src& src_of(const Batch& bt, int c, u32 b, i64& r) {
   r = bt.sel_row[b];
@@ -161,12 +209,45 @@ TFR_HOSTDEV inline u64 element(const Batch& bt, int c, u32 b, u32 t, u32 j) {
   return cell_elem(bt.cols[c], cell_of(bt, c, b, t), j);
 }
 
-// The per-row words of (column, b): outer count, error cause, truncation.
-TFR_HOSTDEV inline RowWords row_words(const Batch& bt, int c, u32 b) {
+// Raw counts of row b of a RAGGED* column: its items (RAGGED2D) and its
+// values, after the max_len cut (RAGGED). Absent and empty rows are 0.
+struct Counts {
+  i64 items;
+  i64 values;
+  bool cut;
+};
+
+TFR_HOSTDEV inline Counts row_counts(const Batch& bt, int c, u32 b) {
   const Col& col = bt.cols[c];
   i64 r;
   const Src& s = src_of(bt, c, b, r);
+  Counts n{0, 0, false};
+  if (!s.presence[r]) return n;
+  if (col.mode == CM_RAGGED) {
+    const i64 v = s.row_off[r + 1] - s.row_off[r];
+    n.cut = v > col.L;
+    n.values = n.cut ? col.L : v;
+    return n;
+  }
+  const bool by = col.flags & CF_BYTES;
+  const i64* outer_off = by ? s.row_off : s.list_off;
+  const i64* inner_off = by ? s.elem_off : s.sub_off;
+  const i64 o0 = outer_off[r];
+  n.items = outer_off[r + 1] - o0;
+  n.values = inner_off[o0 + n.items] - inner_off[o0];
+  return n;
+}
+
+// The per-row words of (column, b): outer count, error cause, truncation.
+TFR_HOSTDEV inline RowWords row_words(const Batch& bt, int c, u32 b) {
+  const Col& col = bt.cols[c];
   RowWords w{0, CC_OK, false};
+  if (is_ragged(col)) {
+    w.truncated = row_counts(bt, c, b).cut;
+    return w;
+  }
+  i64 r;
+  const Src& s = src_of(bt, c, b, r);
   const bool present = s.presence[r] != 0;
   bool over = false;
   if (col.mode == CM_PADDED2D) {
@@ -202,23 +283,31 @@ TFR_HOSTDEV inline RowWords row_words(const Batch& bt, int c, u32 b) {
   return w;
 }
 
-// Side effects of the lane that owns element 0 of row b of column c. A row
-// cut in several columns is counted by the first of them only, so the
-// counter counts rows and takes at most B adds per batch.
+template <class Ops>
+TFR_HOSTDEV inline void raise(const Batch& bt, int c, u32 b, int cause) {
+  Ops::min64(bt.status, ((u64)b << 16) | ((u64)c << 8) | (u64)cause);
+}
+
+// Row b is cut in column c. A row cut in several columns is counted by the
+// first of them only, so the counter counts rows and takes at most B adds
+// per batch.
+template <class Ops>
+TFR_HOSTDEV inline void count_cut(const Batch& bt, int c, u32 b) {
+  bool first = true;
+  for (int p = 0; p < c && first; ++p)
+    if (bt.cols[p].flags & CF_TRUNCATE)
+      first = !row_words(bt, p, b).truncated;
+  if (first) Ops::inc64(bt.status + 1);
+}
+
+// Side effects of the lane that owns element 0 of row b of dense column c.
 template <class Ops>
 TFR_HOSTDEV inline void emit_row(const Batch& bt, int c, u32 b) {
   const Col& col = bt.cols[c];
   const RowWords w = row_words(bt, c, b);
   if (col.outer) col.outer[b] = w.outer;
-  if (w.cause)
-    Ops::min64(bt.status, ((u64)b << 16) | ((u64)c << 8) | (u64)w.cause);
-  if (w.truncated) {
-    bool first = true;
-    for (int p = 0; p < c && first; ++p)
-      if (bt.cols[p].flags & CF_TRUNCATE)
-        first = !row_words(bt, p, b).truncated;
-    if (first) Ops::inc64(bt.status + 1);
-  }
+  if (w.cause) raise<Ops>(bt, c, b, w.cause);
+  if (w.truncated) count_cut<Ops>(bt, c, b);
 }
 
 // Element 0 of cell (b, t): its length word, and for t == 0 the row's words.
@@ -241,9 +330,11 @@ TFR_HOSTDEV inline void do_unit(const Batch& bt, int c, u32 u) {
     const u32 t = bt_ % T, b = bt_ / T;
     const Cell cell = cell_of(bt, c, b, t);
     const u64 v = cell_elem(col, cell, j);
-    if (col.esize == 8) {
+    if (col.esize == 8 && !narrows(col)) {
       reinterpret_cast<u64*>(col.out)[u] = v;
     } else {
+      if (narrows(col) && j < cell.n && (i64)v != (i64)(i32)v)
+        raise<Ops>(bt, c, b, CC_RANGE);
       reinterpret_cast<u32*>(col.out)[u] = (u32)v;
     }
     if (j == 0) emit_cell_head<Ops>(bt, c, b, t, cell);
@@ -279,6 +370,163 @@ TFR_HOSTDEV inline void do_unit(const Batch& bt, int c, u32 u) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// RAGGED / RAGGED2D
+// ---------------------------------------------------------------------------
+
+TFR_HOSTDEV inline i64 min64v(i64 a, i64 b) { return a < b ? a : b; }
+
+// Value units of a ragged column: elements, or 8-byte words of a byte column.
+TFR_HOSTDEV inline i64 value_units(const Col& col) {
+  return col.esize == 1 ? (col.cap + 7) / 8 : col.cap;
+}
+
+// Step one, per row: n are the row's counts, v_end / i_end the inclusive
+// prefix sums of values / items over the batch rows up to b.
+template <class Ops>
+TFR_HOSTDEV inline void ragged_row(const Batch& bt, int c, u32 b,
+                                   const Counts& n, i64 v_end, i64 i_end) {
+  const Col& col = bt.cols[c];
+  const bool two = col.mode == CM_RAGGED2D;
+  col.raw[b + 1] = v_end;
+  if (two) col.raw[bt.B + 1 + b + 1] = i_end;
+  col.len[b + 1] =
+      (i32)(two ? min64v(i_end, col.icap) : min64v(v_end, col.cap));
+  // the first row whose end passes a capacity; its start did not
+  const bool over_v = v_end > col.cap && v_end - n.values <= col.cap;
+  const bool over_i = two && i_end > col.icap && i_end - n.items <= col.icap;
+  if (over_v || over_i) raise<Ops>(bt, c, b, CC_CAPACITY);
+  if (n.cut) count_cut<Ops>(bt, c, b);
+}
+
+template <class Ops>
+TFR_HOSTDEV inline void ragged_row0(const Batch& bt, int c) {
+  const Col& col = bt.cols[c];
+  col.raw[0] = 0;
+  if (col.mode == CM_RAGGED2D) col.raw[bt.B + 1] = 0;
+  col.len[0] = 0;
+}
+
+// Largest b with off[b] <= p, for 0 <= p < off[B]: the (non-empty) row that
+// position p lies in.
+TFR_HOSTDEV inline u32 find_row(const i64* off, u32 B, i64 p) {
+  u32 lo = 0, hi = B;
+  while (hi - lo > 1) {
+    const u32 mid = lo + (hi - lo) / 2;
+    if (off[mid] <= p)
+      lo = mid;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+// What a unit needs of the batch row its first position lies in. Values:
+// position p of the batch is read at addr + p*esize, aux is the row's raw
+// end. Items: the raw value offset of item q is *(i64*)(addr + q*8) + aux.
+// The address is kept as an integer: it may lie before its array.
+struct RowRef {
+  u64 addr;
+  i64 aux;
+};
+
+TFR_HOSTDEV inline RowRef value_ref(const Batch& bt, int c, u32 b) {
+  const Col& col = bt.cols[c];
+  i64 r;
+  const Src& s = src_of(bt, c, b, r);
+  i64 v0;
+  if (col.mode == CM_RAGGED) {
+    v0 = s.row_off[r];
+  } else {
+    const bool by = col.flags & CF_BYTES;
+    v0 = (by ? s.elem_off : s.sub_off)[(by ? s.row_off : s.list_off)[r]];
+  }
+  return RowRef{(u64)s.values + (u64)((v0 - col.raw[b]) * col.esize),
+                col.raw[b + 1]};
+}
+
+TFR_HOSTDEV inline RowRef item_ref(const Batch& bt, int c, u32 b) {
+  const Col& col = bt.cols[c];
+  i64 r;
+  const Src& s = src_of(bt, c, b, r);
+  const bool by = col.flags & CF_BYTES;
+  const i64* inner_off = by ? s.elem_off : s.sub_off;
+  const i64 o0 = (by ? s.row_off : s.list_off)[r];
+  return RowRef{(u64)inner_off + (u64)((o0 - col.raw[bt.B + 1 + b]) * 8),
+                col.raw[b] - inner_off[o0]};
+}
+
+// Value unit u of ragged column c; b is the batch row that the unit's first
+// position lies in and rr its value_ref (both unused when that position is
+// past the batch's total). WORDS: a word of a byte column that lies inside
+// one row is read as two aligned 8-byte loads and funnel-shifted; an aligned
+// word that holds a wanted byte lies in that byte's page, so the over-read
+// cannot fault. Other words, and the host, go byte by byte.
+template <class Ops, bool WORDS>
+TFR_HOSTDEV inline void ragged_value_unit(const Batch& bt, int c, u32 u, u32 b,
+                                          RowRef rr) {
+  const Col& col = bt.cols[c];
+  const i64 total = col.raw[bt.B];
+  if (col.esize != 1) {
+    const i64 p = u;
+    u64 v = 0;
+    if (p < total) {
+      if (col.esize == 8) {
+        __builtin_memcpy(&v, (const u8*)(rr.addr + (u64)p * 8), 8);
+      } else {
+        u32 w;
+        __builtin_memcpy(&w, (const u8*)(rr.addr + (u64)p * 4), 4);
+        v = w;
+      }
+    }
+    if (col.esize == 8 && !narrows(col)) {
+      reinterpret_cast<u64*>(col.out)[u] = v;
+    } else {
+      if (narrows(col) && (i64)v != (i64)(i32)v)
+        raise<Ops>(bt, c, b, CC_RANGE);
+      reinterpret_cast<u32*>(col.out)[u] = (u32)v;
+    }
+    return;
+  }
+  const i64 p = (i64)u * 8;
+  const u32 cnt = (u32)min64v(8, col.cap - p);
+  u64 word = 0;
+  if (WORDS && p + 8 <= rr.aux) {
+    const u64 a = rr.addr + (u64)p;
+    const u32 mis = (u32)(a & 7);
+    const u64* q = reinterpret_cast<const u64*>(a - mis);
+    word = q[0];
+    if (mis) word = (word >> (8 * mis)) | (q[1] << (64 - 8 * mis));
+  } else {
+    for (u32 k = 0; k < cnt && p + k < total; ++k) {
+      if (p + k >= rr.aux) {
+        while (p + k >= col.raw[b + 1]) ++b;
+        rr = value_ref(bt, c, b);
+      }
+      const u8 byte = *(const u8*)(rr.addr + (u64)(p + k));
+      word |= (u64)byte << (8 * k);
+    }
+  }
+  if (cnt == 8) {
+    reinterpret_cast<u64*>(col.out)[u] = word;
+  } else {
+    for (u32 k = 0; k < cnt; ++k) col.out[p + k] = (u8)(word >> (8 * k));
+  }
+}
+
+// item_offsets entry q (0..icap) of RAGGED2D column c; rr is the item_ref of
+// the batch row that owns item q (unused past the last item).
+TFR_HOSTDEV inline void ragged_item_unit(const Batch& bt, int c, u32 q,
+                                         RowRef rr) {
+  const Col& col = bt.cols[c];
+  i64 v = col.raw[bt.B];
+  if ((i64)q < col.raw[2 * bt.B + 1]) {
+    __builtin_memcpy(&v, (const u8*)(rr.addr + (u64)q * 8), 8);
+    v += rr.aux;
+  }
+  col.outer[q] = (i32)min64v(v, col.cap);
+}
+
 // Host atomics: the host path is one thread.
 struct HostOps {
   static void min64(u64* p, u64 v) {
@@ -287,9 +535,50 @@ struct HostOps {
   static void inc64(u64* p) { *p += 1; }
 };
 
+// A ragged column on the host: a serial prefix sum, then the units in order
+// with a cursor for the row of each.
+inline void host_ragged(const Batch& bt, int c) {
+  const Col& col = bt.cols[c];
+  const u32 B = (u32)bt.B;
+  ragged_row0<HostOps>(bt, c);
+  i64 v = 0, i = 0;
+  for (u32 b = 0; b < B; ++b) {
+    const Counts n = row_counts(bt, c, b);
+    v += n.values;
+    i += n.items;
+    ragged_row<HostOps>(bt, c, b, n, v, i);
+  }
+  const i64 g = col.esize == 1 ? 8 : 1;
+  u32 b = 0;
+  for (i64 u = 0, nu = value_units(col); u < nu; ++u) {
+    RowRef rr{0, 0};
+    if (u * g < v) {
+      while (u * g >= col.raw[b + 1]) ++b;
+      rr = value_ref(bt, c, b);
+    }
+    ragged_value_unit<HostOps, false>(bt, c, (u32)u, b, rr);
+  }
+  if (col.mode != CM_RAGGED2D) return;
+  const i64* ioff = col.raw + B + 1;
+  b = 0;
+  for (i64 q = 0; q <= col.icap; ++q) {
+    RowRef rr{0, 0};
+    if (q < i) {
+      while (q >= ioff[b + 1]) ++b;
+      rr = item_ref(bt, c, b);
+    }
+    ragged_item_unit(bt, c, (u32)q, rr);
+  }
+}
+
 inline void host_run(const Batch& bt) {
-  for (int c = 0; c < (int)bt.ncols; ++c)
+  for (int c = 0; c < (int)bt.ncols; ++c) {
+    if (is_ragged(bt.cols[c])) {
+      host_ragged(bt, c);
+      continue;
+    }
     for (i64 u = 0; u < bt.cols[c].units; ++u) do_unit<HostOps>(bt, c, (u32)u);
+  }
 }
 
 }  // namespace collate

@@ -879,7 +879,7 @@ void host_collate(py::array_t<i64, py::array::c_style> src,
   const i64 ncols = cols.size() / cl::kColWords;
   const i64 B = sel_slot.size();
   if (ncols <= 0 || ncols > cl::kMaxCols || cols.size() % cl::kColWords)
-    throw std::invalid_argument("host_collate: 1..64 columns of 12 words");
+    throw std::invalid_argument("host_collate: 1..64 columns of 16 words");
   if (sel_row.size() != B || status.size() != 2 ||
       src.size() % (ncols * cl::kSrcWords))
     throw std::invalid_argument("host_collate: table sizes disagree");

@@ -1,4 +1,5 @@
-"""Dense batches from ragged decoded shards: feature specs and the collator.
+"""Dense or packed batches from ragged decoded shards: feature specs and the
+collator.
 
 The decoder's wire form (columnar.py) is ragged: flat values plus offsets.
 A model takes `[B]`, `[B, L]` or `[B, T, L]`. The specs below say, per column,
@@ -13,9 +14,24 @@ FixedLenFeature / VarLenFeature), and `collate_batch` gathers B rows, each a
                                           name: [B, T, L], name_outer: int32
                                           [B], name_len: int32 [B, T]
 
-The semantics are csrc/collate_core.h's, run by the gfx950 kernel
-(csrc/hip/collate.hip, one launch and one host wait per batch) or by the
-same core in host loops (`_native.host_collate`).
+or which packed form, values plus `cu_seqlens`-style offsets, with shapes
+fixed by the spec (so `out=` tensors and graph capture keep working):
+
+    Ragged(capacity=None, max_len=None)   name: [capacity] values in batch
+                                          order, name_offsets: int32 [B+1]
+    Ragged2D(item_capacity, value_capacity)
+                                          name: [value_capacity],
+                                          name_item_offsets: int32
+                                          [item_capacity+1], name_offsets:
+                                          int32 [B+1] (over items)
+
+Every spec takes `dtype="int32"` on an int64 column: the kernel narrows, and
+a value outside int32 is a RANGE error.
+
+The semantics are csrc/collate_core.h's, run by the gfx950 kernels
+(csrc/hip/collate.hip: one launch for the dense columns, two more for all
+packed ones, one host wait per batch) or by the same core in host loops
+(`_native.host_collate`).
 """
 
 from __future__ import annotations
@@ -32,14 +48,17 @@ from .columnar import RecordBatch, wire_fields
 from .schema import (KIND_BYTES, KIND_FLOAT, KIND_INT64, NullType, StructType,
                      is_sequence_field, wire_kind_of)
 
-__all__ = ["FixedLen", "Padded", "Padded2D", "Collator", "collate_batch",
-           "plan_columns", "CAUSES"]
+__all__ = ["FixedLen", "Padded", "Padded2D", "Ragged", "Ragged2D", "Collator",
+           "collate_batch", "plan_columns", "CAUSES"]
 
-CM_FIXED, CM_PADDED, CM_PADDED2D = 0, 1, 2
-CC_MISSING, CC_LENGTH = 1, 2
+CM_FIXED, CM_PADDED, CM_PADDED2D, CM_RAGGED, CM_RAGGED2D = 0, 1, 2, 3, 4
+CC_MISSING, CC_LENGTH, CC_RANGE, CC_CAPACITY = 1, 2, 3, 4
 CAUSES = {CC_MISSING: "MISSING (row absent or empty and the spec has no "
                       "default)",
-          CC_LENGTH: "LENGTH (row's value count does not fit the spec)"}
+          CC_LENGTH: "LENGTH (row's value count does not fit the spec)",
+          CC_RANGE: "RANGE (a value does not fit the int32 output)",
+          CC_CAPACITY: "CAPACITY (the batch's total passes the spec's "
+                       "capacity with this row)"}
 CF_DEFAULT, CF_TRUNCATE, CF_BYTES = 1, 2, 4
 STATUS_CLEAN = (1 << 64) - 1
 
@@ -55,6 +74,7 @@ class FixedLen:
     An absent or empty row takes `default` when one is given."""
     length: Optional[int] = None
     default: Optional[Union[int, float]] = None
+    dtype: Optional[str] = None
 
 
 @dataclass(frozen=True)
@@ -64,6 +84,7 @@ class Padded:
     max_len: int
     pad: Union[int, float] = 0
     truncate: bool = False
+    dtype: Optional[str] = None
 
 
 @dataclass(frozen=True)
@@ -74,6 +95,29 @@ class Padded2D:
     max_inner: int
     pad: Union[int, float] = 0
     truncate: bool = False
+    dtype: Optional[str] = None
+
+
+@dataclass(frozen=True)
+class Ragged:
+    """The rows' values back to back in `capacity` elements (zero past the
+    batch's total) and int32 offsets `[B+1]`. `max_len` cuts each row to its
+    first values (counted as truncated); alone it sets the capacity to
+    `B * max_len`, which cannot overflow. A total above the capacity is a
+    CAPACITY error at the first row whose end passes it."""
+    capacity: Optional[int] = None
+    max_len: Optional[int] = None
+    dtype: Optional[str] = None
+
+
+@dataclass(frozen=True)
+class Ragged2D:
+    """The rows' items (strings of a bytes column, lists of a FeatureList)
+    back to back: values `[value_capacity]`, int32 item offsets
+    `[item_capacity+1]` into them, int32 row offsets `[B+1]` into the items."""
+    item_capacity: int
+    value_capacity: int
+    dtype: Optional[str] = None
 
 
 _NP_DTYPE = {KIND_INT64: np.int64, KIND_FLOAT: np.float32, KIND_BYTES: np.uint8}
@@ -82,9 +126,12 @@ _TORCH_DTYPE = {KIND_INT64: torch.int64, KIND_FLOAT: torch.float32,
 _ESIZE = {KIND_INT64: 8, KIND_FLOAT: 4, KIND_BYTES: 1}
 
 
-def _fill_bits(kind: int, value, name: str) -> int:
-    """`value` in the column's number format, as the low bytes of a word."""
+def _fill_bits(kind: int, value, name: str, narrow: bool = False) -> int:
+    """`value` in the column's output number format (`narrow`: int32), as
+    the low bytes of a word."""
     try:
+        if kind == KIND_INT64 and narrow:
+            return struct.unpack("<I", struct.pack("<i", int(value)))[0]
         if kind == KIND_INT64:
             return struct.unpack("<Q", struct.pack("<q", int(value)))[0]
         if kind == KIND_FLOAT:
@@ -107,10 +154,27 @@ class _Plan:
     fill: int
     flags: int
     squeeze: bool   # FixedLen(length=None): output [B], not [B, 1]
+    narrow: bool = False  # dtype="int32": int64 values stored as int32
+    cap: int = 0    # Ragged*: value capacity (0: B * L)
+    icap: int = 0   # Ragged2D: item capacity
+
+    @property
+    def ragged(self) -> bool:
+        return self.mode >= CM_RAGGED
+
+    def capacity(self, B: int) -> int:
+        return self.cap or B * self.L
 
     def shapes(self, B: int) -> Dict[str, tuple]:
         """Output name -> (shape, numpy dtype) for a batch of B rows."""
-        dt = _NP_DTYPE[self.kind]
+        dt = np.int32 if self.narrow else _NP_DTYPE[self.kind]
+        if self.mode == CM_RAGGED:
+            return {self.name: ((self.capacity(B),), dt),
+                    self.name + "_offsets": ((B + 1,), np.int32)}
+        if self.mode == CM_RAGGED2D:
+            return {self.name: ((self.cap,), dt),
+                    self.name + "_item_offsets": ((self.icap + 1,), np.int32),
+                    self.name + "_offsets": ((B + 1,), np.int32)}
         if self.mode == CM_FIXED:
             return {self.name: ((B,) if self.squeeze else (B, self.L), dt)}
         if self.mode == CM_PADDED:
@@ -126,6 +190,30 @@ def _positive(v, what: str, name: str) -> int:
         raise ValueError(f"column '{name}': {what} must be a positive integer, "
                          f"got {v!r}")
     return int(v)
+
+
+def _capacity(v, what: str, name: str) -> int:
+    v = _positive(v, what, name)
+    if v >= 1 << 31:
+        raise ValueError(f"column '{name}': {what} must be below 2^31, got "
+                         f"{v}")
+    return v
+
+
+_NO_CUT = 1 << 62  # Ragged without max_len: no row is that long
+
+
+def _narrow(spec, kind: int, name: str) -> bool:
+    """The spec's `dtype`: None, or "int32" on an int64 column."""
+    if spec.dtype is None:
+        return False
+    if spec.dtype != "int32":
+        raise ValueError(f"column '{name}': dtype must be None or 'int32', "
+                         f"got {spec.dtype!r}")
+    if kind != KIND_INT64:
+        raise ValueError(f"column '{name}': dtype='int32' takes an int64 "
+                         f"column")
+    return True
 
 
 def plan_columns(schema: StructType, features: Dict[str, Any]) -> List[_Plan]:
@@ -149,42 +237,62 @@ def plan_columns(schema: StructType, features: Dict[str, Any]) -> List[_Plan]:
         f = wf[by_name[name]]
         kind = wire_kind_of(f.dataType)
         seq = is_sequence_field(f.dataType)
-        if isinstance(spec, (FixedLen, Padded)):
+        if isinstance(spec, (FixedLen, Padded, Ragged)):
             if seq or kind == KIND_BYTES:
                 raise ValueError(
                     f"column '{name}': {type(spec).__name__} takes an int64 "
                     f"or float column that is not a FeatureList, not "
                     f"{f.dataType.simple_string()}")
-            if isinstance(spec, FixedLen):
+            nar = _narrow(spec, kind, name)
+            if isinstance(spec, Ragged):
+                if spec.capacity is None and spec.max_len is None:
+                    raise ValueError(f"column '{name}': Ragged needs a "
+                                     f"capacity or a max_len")
+                cut = spec.max_len is not None
+                plans.append(_Plan(
+                    name, by_name[name], kind, CM_RAGGED, 1,
+                    _capacity(spec.max_len, "max_len", name) if cut
+                    else _NO_CUT, 0, CF_TRUNCATE if cut else 0, False, nar,
+                    0 if spec.capacity is None
+                    else _capacity(spec.capacity, "capacity", name)))
+            elif isinstance(spec, FixedLen):
                 L = 1 if spec.length is None else _positive(
                     spec.length, "length", name)
                 has = spec.default is not None
                 plans.append(_Plan(
                     name, by_name[name], kind, CM_FIXED, 1, L,
-                    _fill_bits(kind, spec.default if has else 0, name),
-                    CF_DEFAULT if has else 0, spec.length is None))
+                    _fill_bits(kind, spec.default if has else 0, name, nar),
+                    CF_DEFAULT if has else 0, spec.length is None, nar))
             else:
                 plans.append(_Plan(
                     name, by_name[name], kind, CM_PADDED, 1,
                     _positive(spec.max_len, "max_len", name),
-                    _fill_bits(kind, spec.pad, name),
-                    CF_TRUNCATE if spec.truncate else 0, False))
-        elif isinstance(spec, Padded2D):
+                    _fill_bits(kind, spec.pad, name, nar),
+                    CF_TRUNCATE if spec.truncate else 0, False, nar))
+        elif isinstance(spec, (Padded2D, Ragged2D)):
             if seq == (kind == KIND_BYTES):
                 raise ValueError(
-                    f"column '{name}': Padded2D takes a numeric FeatureList "
-                    f"or a bytes column that is not a FeatureList, not "
-                    f"{f.dataType.simple_string()}")
+                    f"column '{name}': {type(spec).__name__} takes a numeric "
+                    f"FeatureList or a bytes column that is not a "
+                    f"FeatureList, not {f.dataType.simple_string()}")
+            nar = _narrow(spec, kind, name)
+            by = CF_BYTES if kind == KIND_BYTES else 0
+            if isinstance(spec, Ragged2D):
+                plans.append(_Plan(
+                    name, by_name[name], kind, CM_RAGGED2D, 1, 1, 0, by,
+                    False, nar,
+                    _capacity(spec.value_capacity, "value_capacity", name),
+                    _capacity(spec.item_capacity, "item_capacity", name)))
+                continue
             plans.append(_Plan(
                 name, by_name[name], kind, CM_PADDED2D,
                 _positive(spec.max_outer, "max_outer", name),
                 _positive(spec.max_inner, "max_inner", name),
-                _fill_bits(kind, spec.pad, name),
-                (CF_TRUNCATE if spec.truncate else 0)
-                | (CF_BYTES if kind == KIND_BYTES else 0), False))
+                _fill_bits(kind, spec.pad, name, nar),
+                (CF_TRUNCATE if spec.truncate else 0) | by, False, nar))
         else:
             raise ValueError(f"column '{name}': {spec!r} is not a FixedLen, "
-                             f"Padded or Padded2D spec")
+                             f"Padded, Padded2D, Ragged or Ragged2D spec")
     return plans
 
 
@@ -219,6 +327,7 @@ class Collator:
         self._keep: list = []
         self._rows = np.zeros(0, np.int64)
         self._src_table = None
+        self._scratch = None  # device: raw offsets of the ragged columns
 
     # -- window -----------------------------------------------------------
     def set_window(self, sources: Sequence[Optional[RecordBatch]]):
@@ -295,7 +404,11 @@ class Collator:
                 f"batch row {b}: row {int(sel_row[b])} out of range for slot "
                 f"{int(sel_slot[b])} ({int(self._rows[sel_slot[b]])} rows)")
         for p in self.plans:
-            if B * p.T * p.L >= 1 << 31:
+            if p.ragged:
+                if p.capacity(B) >= 1 << 31:
+                    raise ValueError(f"column '{p.name}': {p.capacity(B)} "
+                                     f"elements do not fit one batch (2^31)")
+            elif B * p.T * p.L >= 1 << 31:
                 raise ValueError(f"column '{p.name}': {B}x{p.T}x{p.L} "
                                  f"elements do not fit one batch (2^31)")
         return sel_slot.astype(np.int32), sel_row.astype(np.int64), B
@@ -326,11 +439,34 @@ class Collator:
                     f"and dtype {np.dtype(dt).name}")
         return dict(out)
 
-    def _col_table(self, B: int, outs: dict) -> (np.ndarray, int):
+    def _scratch_words(self, B: int) -> int:
+        """Raw 64-bit offsets of the ragged columns: [B+1] per level."""
+        return sum((B + 1) * (2 if p.mode == CM_RAGGED2D else 1)
+                   for p in self.plans if p.ragged)
+
+    def _col_table(self, B: int, outs: dict, scratch: int):
+        """-> (table, dense tiles, ragged columns, ragged tiles); `scratch`
+        is the address of `_scratch_words(B)` words."""
         table = np.zeros((len(self.plans), _COL_WORDS), np.uint64)
-        tile0 = 0
+        tile0 = rtile0 = nragged = 0
         for c, p in enumerate(self.plans):
             esize = _ESIZE[p.kind]
+            osize = 4 if p.narrow else esize
+            if p.ragged:
+                cap = p.capacity(B)
+                units = (cap + 7) // 8 if esize == 1 else cap
+                io = outs.get(p.name + "_item_offsets")
+                if io is not None:
+                    units = max(units, p.icap + 1)
+                table[c] = [p.mode, esize, 1, p.L, 0, p.flags,
+                            outs[p.name].data_ptr(),
+                            outs[p.name + "_offsets"].data_ptr(),
+                            io.data_ptr() if io is not None else 0,
+                            tile0, units, osize, scratch, cap, p.icap, rtile0]
+                scratch += 8 * (B + 1) * (2 if io is not None else 1)
+                rtile0 += (units + _TILE_UNITS - 1) // _TILE_UNITS
+                nragged += 1
+                continue
             elems = B * p.T * p.L
             units = (elems + 7) // 8 if esize == 1 else elems
             ln = outs.get(p.name + "_len")
@@ -339,9 +475,9 @@ class Collator:
                         outs[p.name].data_ptr(),
                         ln.data_ptr() if ln is not None else 0,
                         outer.data_ptr() if outer is not None else 0,
-                        tile0, units, 0]
+                        tile0, units, osize, 0, 0, 0, rtile0]
             tile0 += (units + _TILE_UNITS - 1) // _TILE_UNITS
-        return table.view(np.int64).reshape(-1), tile0
+        return table.view(np.int64).reshape(-1), tile0, nragged, rtile0
 
     # -- one batch ----------------------------------------------------------
     def launch(self, sel_slot, sel_row, out: Optional[dict] = None):
@@ -353,12 +489,23 @@ class Collator:
             raise ValueError("set_window() first")
         sel_slot, sel_row, B = self._check_selection(sel_slot, sel_row)
         outs = self._outputs(B, out)
-        cols, ntiles = self._col_table(B, outs)
+        nscratch = self._scratch_words(B)
         if self.engine == "cpu":
+            scratch = np.empty(max(nscratch, 1), np.int64)
+            cols = self._col_table(B, outs, scratch.ctypes.data)[0]
             status = np.array([STATUS_CLEAN, 0], np.uint64)
             _native.host_collate(self._src_table, cols, sel_slot, sel_row,
                                  status)
             return (outs, status, None, None)
+        # the raw-offset scratch, written by the scan and read by the gather
+        # of one batch: allocated once per collator (it grows with B), and
+        # shared by the batches in flight, which one stream runs in order
+        if nscratch > (0 if self._scratch is None else self._scratch.numel()):
+            self._scratch = torch.empty(nscratch, dtype=torch.int64,
+                                        device="cuda")
+        scratch = self._scratch if nscratch else None
+        cols, ntiles, nragged, rtiles = self._col_table(
+            B, outs, scratch.data_ptr() if nscratch else 0)
         # one upload: status init | sel_row | column table | sel_slot
         nc = cols.size
         words = 2 + B + nc + (B + 1) // 2
@@ -371,16 +518,21 @@ class Collator:
         dev = host.to("cuda", non_blocking=True)
         base = dev.data_ptr()
         stream = torch.cuda.current_stream()
-        _native.gpu_collate_rows(
-            self._src_table.data_ptr(), base + 8 * (2 + B),
-            base + 8 * (2 + B + nc), base + 16, len(self.plans), B, ntiles,
-            base, stream.cuda_stream)
-        self.launches += 1
+        tables = (self._src_table.data_ptr(), base + 8 * (2 + B),
+                  base + 8 * (2 + B + nc), base + 16, len(self.plans), B)
+        if ntiles:
+            _native.gpu_collate_rows(*tables, ntiles, base,
+                                     stream.cuda_stream)
+            self.launches += 1
+        if nragged:
+            _native.gpu_collate_ragged(*tables, nragged, rtiles, base,
+                                       stream.cuda_stream)
+            self.launches += 2
         back = torch.empty(2, dtype=torch.int64, pin_memory=True)
         back.copy_(dev[:2], non_blocking=True)
         done = torch.cuda.Event()
         done.record(stream)
-        return (outs, back, done, (self._keep, self._src_table, dev))
+        return (outs, back, done, (self._keep, self._src_table, dev, scratch))
 
     def finish(self, handle):
         """Wait for a launched batch -> (outputs, status): status[0] is
@@ -416,7 +568,7 @@ def collate_batch(sources: Sequence[Optional[RecordBatch]], sel_slot, sel_row,
                   specs: Dict[str, Any], engine: str = "cpu",
                   out: Optional[dict] = None, return_status: bool = False):
     """Collate the rows `(sel_slot[b], sel_row[b])` of `sources` into dense
-    tensors per `specs` (host tensors for engine "cpu", device tensors for
+    or packed tensors per `specs` (host tensors for engine "cpu", device tensors for
     "gpu", whose sources must be device-resident).
 
     Raises ValueError for a bad selection or output before anything runs, and

@@ -11,15 +11,20 @@ torch.distributed ranks and DataLoader workers round-robin.
     for batch in ds:           # dict: name -> values tensor,
         ...                    #       name+"_offsets" -> row offsets (ragged)
 
-TFRecordBatchDataset goes the rest of the way: dense, shuffled batches of a
-fixed size, collated on the device from a window of decoded shards
-(collate.py; one kernel launch and one host wait per batch).
+TFRecordBatchDataset goes the rest of the way: shuffled batches of a fixed
+size, dense or packed (values + offsets), collated on the device from a
+window of decoded shards (collate.py; one kernel launch per batch, two more
+when it has packed columns, and one host wait).
 
     ds = TFRecordBatchDataset(path, features={"id": FixedLen(),
                                               "ints": Padded(8)},
                               batch_size=8192, shuffle_window=4)
     for batch in ds:           # dict: name -> [B], [B, L] or [B, T, L]
         ...
+
+    features={"tokens": Ragged(capacity=1 << 20, dtype="int32")}
+                               # tokens: int32 [capacity], tokens_offsets:
+                               # int32 [B+1] (cu_seqlens)
 """
 
 from __future__ import annotations
@@ -36,10 +41,10 @@ from .io import paths as P
 from .schema import KIND_BYTES, StructType
 from .columnar import RecordBatch
 from .collate import (STATUS_CLEAN, Collator, FixedLen, Padded, Padded2D,
-                      plan_columns)
+                      Ragged, Ragged2D, plan_columns)
 
 __all__ = ["TFRecordIterableDataset", "TFRecordBatchDataset", "FixedLen",
-           "Padded", "Padded2D"]
+           "Padded", "Padded2D", "Ragged", "Ragged2D"]
 
 
 def _as_torch(x, device):
@@ -281,9 +286,10 @@ class _Slot:
 
 
 class TFRecordBatchDataset(_ShardSource):
-    """Dense batches of exactly `batch_size` rows, shuffled through a window
-    of decoded shards and collated per `features` (name -> FixedLen / Padded
-    / Padded2D, see collate.py).
+    """Batches of exactly `batch_size` rows, shuffled through a window of
+    decoded shards and collated per `features` (name -> FixedLen / Padded /
+    Padded2D for dense tensors, Ragged / Ragged2D for values + offsets, see
+    collate.py).
 
     The window holds up to `shuffle_window` decoded shards; each has a
     seeded permutation of its rows. A batch draws `batch_size` rows
@@ -296,8 +302,9 @@ class TFRecordBatchDataset(_ShardSource):
     listing order; only the spec'd columns are decoded.
 
     engine "gpu": shards decode on the device and stay there; per batch only
-    the selection crosses the link, one kernel gathers every column, and the
-    iterator waits once, on the status words. `truncated_rows` accumulates
+    the selection crosses the link, one kernel gathers every dense column
+    (two more launches cover all packed columns), and the iterator waits
+    once, on the status words. `truncated_rows` accumulates
     over an iteration; `last_stats` holds the last iteration's batches,
     kernel launches and host waits.
     """
