@@ -188,6 +188,17 @@ void pread_parallel(int fd, uintptr_t ptr, i64 n, i64 file_off) {
   if (e) throw std::runtime_error("pread failed: " + std::string(strerror(-e)));
 }
 
+// Host-to-host copy split across the IO pool: the sliced write's staging
+// buffer into the file's own (unregistered) mapping. Writes through a
+// mapping do not take the inode lock that serializes pwrite() to one file.
+void memcpy_parallel(uintptr_t dst, uintptr_t src, i64 n) {
+  py::gil_scoped_release rel;
+  (void)IOPool::instance().run_parts(n, 256 << 10, [=](i64 o, i64 m) {
+    memcpy((u8*)dst + o, (const u8*)src + o, (size_t)m);
+    return 0;
+  });
+}
+
 struct BufView {
   const u8* data;
   i64 size;
@@ -935,6 +946,8 @@ void register_collate(py::module_& m);  // defined in csrc/hip/collate.hip
 
 PYBIND11_MODULE(_native, m) {
   m.doc() = "MI355X-native TFRecord codec (host + gfx950 kernels)";
+  m.def("memcpy_parallel", &memcpy_parallel, py::arg("dst"), py::arg("src"),
+        py::arg("n"));
   m.def("pwrite_parallel", &pwrite_parallel, py::arg("fd"), py::arg("ptr"),
         py::arg("n"), py::arg("file_off"),
         "Multi-threaded pwrite of [ptr, ptr+n) to fd at file_off");

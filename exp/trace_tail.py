@@ -14,6 +14,12 @@ time; for the chosen read (default: the last) also the kernel list from the
 first copy's issue and, per slice, the wall time of the slice's kernel chain
 (from its COUNT pass to the last kernel before the next COUNT pass) next to
 the slice period (the distance between two landings).
+
+--writes prints the write side instead. A write starts at its first kernel
+(size_records) and ends where the next read's first slice copy is issued.
+Per write: the head (first kernel's start to the start of the first large
+device-to-host copy), the end (last large copy's end to the end of the
+call's last device activity) and what lies in each.
 """
 
 import argparse
@@ -86,6 +92,57 @@ def landings(slice_copies, split=True):
     return sorted(out)
 
 
+def find_writes(kernels, copies):
+    """[(t0, t1, large D2H copies, kernels, small copies)] per write."""
+    starts = [k[0] for k in kernels if "size_records" in k[2]]
+    reads = [c[0] for c in copies if "HOST_TO_DEVICE" in c[2]
+             and c[1] - c[0] > SLICE_COPY_MS]
+    writes = []
+    for i, t0 in enumerate(starts):
+        t1 = min([r for r in reads if r > t0] + starts[i + 1:i + 2] +
+                 [float("inf")])
+        inside = [c for c in copies if t0 <= c[0] < t1]
+        big = [c for c in inside if "DEVICE_TO_HOST" in c[2]
+               and c[1] - c[0] > SLICE_COPY_MS]
+        ks = [k for k in kernels if t0 <= k[0] < t1]
+        # a copy into pinned (not registered) memory can run as a blit
+        # kernel, which the copy trace does not list
+        blits = [k for k in ks if "copyBuffer" in k[2]
+                 and k[1] - k[0] > SLICE_COPY_MS]
+        big += [(k[0], k[1], "blit") for k in blits]
+        if big:
+            writes.append((t0, t1, big, [k for k in ks if k not in blits],
+                           [c for c in inside if c not in big]))
+    return writes
+
+
+def report_write(idx, w, detail):
+    t0, _, big, ks, small = w
+    first, last = min(c[0] for c in big), max(c[1] for c in big)
+    acts = [(k[0], k[1], k[2]) for k in ks] + \
+           [(c[0], c[1], "copy " + c[2]) for c in small]
+    end = max([a[1] for a in acts] + [last])
+    link = busy([(c[0], c[1]) for c in big])
+    print(f"write {idx}: {len(big)} slice copies, head {first - t0:.3f} ms, "
+          f"copies {last - first:.3f} ms (link busy {link:.3f}), end "
+          f"{end - last:.3f} ms, device span {end - t0:.3f} ms, last "
+          f"device activity starts {max(a[0] for a in acts) - last:.3f} ms "
+          f"after the last copy")
+    if not detail:
+        return
+    print("  in the head (start, end, what) ms from the first kernel:")
+    for s, e, name in sorted(a for a in acts if a[0] < first):
+        print(f"    {s - t0:8.3f} {e - t0:8.3f}  {name[:72]}")
+    print("  after the last copy:")
+    for s, e, name in sorted(a for a in acts if a[1] > last):
+        print(f"    {s - t0:8.3f} {e - t0:8.3f}  {name[:72]}")
+    print("  slice copies (start, end):",
+          [(round(c[0] - t0, 3), round(c[1] - t0, 3)) for c in sorted(big)])
+    print("  emit kernels (start, end):",
+          [(round(k[0] - t0, 3), round(k[1] - t0, 3)) for k in ks
+           if "emit_records" in k[2]])
+
+
 def busy(spans):
     """Length of the union of (start, end) spans."""
     total, cur_s, cur_e = 0.0, None, None
@@ -142,12 +199,21 @@ def main():
                     help="read to print in detail (default: the last)")
     ap.add_argument("--whole-slices", action="store_true",
                     help="the run had TFREC_READ_SPLIT=0: one copy per slice")
+    ap.add_argument("--writes", action="store_true",
+                    help="report the writes' head and end instead")
     args = ap.parse_args()
     kernels, copies = load(args.out_dir)
     dirs = {}
     for c in copies:
         dirs[c[2]] = dirs.get(c[2], 0) + 1
     print("copy directions:", dirs)
+    if args.writes:
+        writes = find_writes(kernels, copies)
+        if not writes:
+            raise SystemExit("no sliced write found in the trace")
+        for i, w in enumerate(writes):
+            report_write(i, w, i == args.read % len(writes))
+        return
     reads = find_reads(kernels, copies)
     if not reads:
         raise SystemExit("no slice copies found in the trace")

@@ -94,6 +94,10 @@ _READ_SLICE = int(os.environ.get("TFREC_READ_SLICE", 32 << 20))
 # holds a pair's work (9.18 ms); TFREC_READ_SPLIT=0 restores that.
 _SPLIT_SLICES = os.environ.get("TFREC_READ_SPLIT", "1") != "0"
 _WRITE_SLICES = int(os.environ.get("TFREC_WRITE_SLICES", 8))
+# Where the file's mapping cannot be registered, the staged sliced write
+# copies its slices into the (unregistered) mapping with the IO pool instead
+# of pwrite()ing them. TFREC_STAGED_MAPPED_WRITE=0: pwrite.
+_STAGED_MAPPED_WRITE = os.environ.get("TFREC_STAGED_MAPPED_WRITE", "1") != "0"
 # Streamed decode: the pipelined reader discovers, chain-checks and
 # structure-scans each slice's records while later slices are still in DMA
 # flight. TFREC_STREAM_DECODE=0 forces the unstreamed path (COUNT under the
@@ -806,11 +810,13 @@ def write_batch_to_file(batch: RecordBatch, path: str,
     file = torch.empty(total, dtype=torch.uint8, device=device)
     err = torch.zeros(2, dtype=torch.int32, device=device)
     ptr, pinned = _native.file_mmap_pinned(path, total, True)
+    mapped = 0
     if not pinned:
         # The mapping cannot be registered: the slices land in a pinned
         # staging buffer of the file's size instead and are written out from
         # there as they arrive. No copy of an earlier call is still in
         # flight into the buffer: every call ends with its copies landed.
+        mapped = ptr if _STAGED_MAPPED_WRITE else 0
         ptr = pinned_buffer("fwrite_slices", total).data_ptr()
     main = torch.cuda.current_stream()
     streams = _dma_streams()
@@ -836,15 +842,40 @@ def write_batch_to_file(batch: RecordBatch, path: str,
         if _SYNC_WRITES:
             _native.file_mmap_sync(path)
     else:
-        _write_staged_slices(path, ptr, landed, total)
+        _write_staged_slices(path, ptr, landed, total, mapped)
     _check_emit_err(err)
     return total
 
 
-def _write_staged_slices(path: str, ptr: int, landed, total: int):
+def _write_staged_slices(path: str, ptr: int, landed, total: int,
+                         mapped: int = 0):
     """The file-side half of a sliced write through pinned staging at `ptr`:
     each slice [b0, b1) is written once its D2H copy (event) has landed, while
-    the later slices are still being emitted and copied."""
+    the later slices are still being emitted and copied. With `mapped`, the
+    file's own mapping of `total` bytes (made, and the file sized, by
+    file_mmap_pinned), the slices are copied into it by the IO pool: pwrite()
+    to one file serializes on the inode lock at one thread's copy speed,
+    stores through the mapping do not."""
+    if mapped:
+        try:
+            # a store to a page the filesystem cannot back ends the process
+            # (SIGBUS) where pwrite() fails with ENOSPC: reserve the blocks
+            # of a file that does not have them all yet
+            if os.stat(path).st_blocks * 512 < total:
+                fd = os.open(path, os.O_RDWR)
+                try:
+                    os.posix_fallocate(fd, 0, total)
+                finally:
+                    os.close(fd)
+            for ev, b0, b1 in landed:
+                ev.synchronize()
+                _native.memcpy_parallel(mapped + b0, ptr + b0, b1 - b0)
+            if _SYNC_WRITES:
+                _native.file_mmap_sync(path)
+        finally:
+            for w in _dma_streams():  # also when a write failed midway
+                w.synchronize()
+        return
     fd = os.open(path, os.O_RDWR | os.O_CREAT, 0o644)
     try:
         for ev, b0, b1 in landed:
