@@ -35,140 +35,13 @@
 #include "snappy_core.h"
 #include "snappy_enc_core.h"
 #include "collate_core.h"
+#include "io_pool.h"
 
 namespace py = pybind11;
 using namespace tfrec;
 
 namespace {
 
-// ---------------------------------------------------------------------------
-// Parallel file IO: persistent pread/pwrite worker pool. A single-threaded
-// write() to tmpfs tops out at ~9 GB/s (one kernel memcpy); splitting each
-// chunk across workers scales that with cores. Used by the GPU engine to keep
-// file IO off the critical path of the H2D/D2H pipeline
-// (spark_tfrecord_amd/engine/gpu.py). Replaces what the reference delegates
-// to Hadoop FS streams (DefaultSource.scala:118-136).
-// ---------------------------------------------------------------------------
-
-class IOPool {
- public:
-  static IOPool& instance() {
-    // leaked on purpose: workers block on the cv forever; destructing the
-    // mutex/cv under them at exit would be UB
-    static IOPool* pool = new IOPool(8);
-    return *pool;
-  }
-
-  // op: false=read, true=write. Splits [off, off+n) across the workers and
-  // blocks until all spans complete. Returns 0 or -errno.
-  int run(bool is_write, int fd, u8* ptr, i64 n, i64 off) {
-    return run_spans(n, [=](i64 o, i64 m) {
-      return is_write ? do_write(fd, ptr + o, m, off + o)
-                      : do_read(fd, ptr + o, m, off + o);
-    });
-  }
-
-  template <typename Fn>
-  int run_spans(i64 n, Fn&& fn) {
-    return run_parts(n, 64 << 10, std::forward<Fn>(fn));
-  }
-
-  // Splits [0, n) into per-worker ranges of at least min_span and runs
-  // fn(offset, count) on the pool; fn returns 0 or an error code (first
-  // nonzero wins). Used for byte IO spans AND record ranges.
-  template <typename Fn>
-  int run_parts(i64 n, i64 min_span, Fn&& fn) {
-    if (n <= 0) return 0;
-    int nspan = (int)nthreads_;
-    i64 span = (n + nspan - 1) / nspan;
-    if (span < min_span) {
-      nspan = (int)((n + min_span - 1) / min_span);
-      if (nspan < 1) nspan = 1;
-      span = (n + nspan - 1) / nspan;
-    }
-    if (nspan == 1) return fn((i64)0, n);  // run inline, skip the pool
-    if (getenv("TFREC_POOL_DEBUG"))
-      fprintf(stderr, "[pool] n=%lld nspan=%d span=%lld\n", (long long)n,
-              nspan, (long long)span);
-    std::atomic<int> err{0};
-    std::atomic<int> left{nspan};
-    {
-      std::unique_lock<std::mutex> lk(mu_);
-      for (int t = 0; t < nspan; ++t) {
-        i64 o = (i64)t * span;
-        i64 m = std::min(span, n - o);
-        tasks_.push_back([=, &err, &left] {
-          int e = fn(o, m);
-          if (e) err.store(e, std::memory_order_relaxed);
-          if (left.fetch_sub(1) == 1) {
-            std::lock_guard<std::mutex> dl(done_mu_);
-            done_cv_.notify_all();
-          }
-        });
-      }
-      cv_.notify_all();
-    }
-    std::unique_lock<std::mutex> dl(done_mu_);
-    done_cv_.wait(dl, [&] { return left.load() == 0; });
-    return err.load();
-  }
-
- private:
-  explicit IOPool(int n) : nthreads_(n) {
-    for (int i = 0; i < n; ++i)
-      workers_.emplace_back([this] { worker(); });
-  }
-
-  static int do_write(int fd, const u8* p, i64 n, i64 off) {
-    while (n > 0) {
-      ssize_t w = ::pwrite(fd, p, (size_t)n, (off_t)off);
-      if (w < 0) {
-        if (errno == EINTR) continue;
-        return -errno;
-      }
-      p += w;
-      n -= w;
-      off += w;
-    }
-    return 0;
-  }
-
-  static int do_read(int fd, u8* p, i64 n, i64 off) {
-    while (n > 0) {
-      ssize_t r = ::pread(fd, p, (size_t)n, (off_t)off);
-      if (r < 0) {
-        if (errno == EINTR) continue;
-        return -errno;
-      }
-      if (r == 0) return -EIO;  // unexpected EOF
-      p += r;
-      n -= r;
-      off += r;
-    }
-    return 0;
-  }
-
-  void worker() {
-    for (;;) {
-      std::function<void()> task;
-      {
-        std::unique_lock<std::mutex> lk(mu_);
-        cv_.wait(lk, [this] { return !tasks_.empty(); });
-        task = std::move(tasks_.back());
-        tasks_.pop_back();
-      }
-      task();
-    }
-  }
-
-  size_t nthreads_;
-  std::vector<std::thread> workers_;
-  std::vector<std::function<void()>> tasks_;
-  std::mutex mu_;
-  std::condition_variable cv_;
-  std::mutex done_mu_;
-  std::condition_variable done_cv_;
-};
 
 void pwrite_parallel(int fd, uintptr_t ptr, i64 n, i64 file_off) {
   int e;
@@ -943,6 +816,7 @@ void register_inflate_foreign(py::module_& m);  // csrc/hip/inflate_foreign.hip
 void register_snappy(py::module_& m);   // defined in csrc/hip/snappy.hip
 void register_snappy_enc(py::module_& m);  // csrc/hip/snappy_enc.hip
 void register_collate(py::module_& m);  // defined in csrc/hip/collate.hip
+void register_stage_upload(py::module_& m);  // csrc/hip/stage_upload.hip
 
 PYBIND11_MODULE(_native, m) {
   m.doc() = "MI355X-native TFRecord codec (host + gfx950 kernels)";
@@ -1026,6 +900,7 @@ PYBIND11_MODULE(_native, m) {
   register_snappy(m);
   register_snappy_enc(m);
   register_collate(m);
+  register_stage_upload(m);
   m.attr("HAS_GPU_KERNELS") = true;
 #else
   m.attr("HAS_GPU_KERNELS") = false;

@@ -13,7 +13,13 @@ kernel's end) and the kernels that end after the last copy with their busy
 time; for the chosen read (default: the last) also the kernel list from the
 first copy's issue and, per slice, the wall time of the slice's kernel chain
 (from its COUNT pass to the last kernel before the next COUNT pass) next to
-the slice period (the distance between two landings).
+the slice period (the distance between two landings). Per read it also
+prints the link's busy share between the first and the last slice copy, the
+largest idle gap between copies, and how long the device had been idle of
+this process's work when the first slice copy started (the end of the write
+before it, then the read's host-side head; an upper bound of that head).
+--min-copy-ms lowers the slice-copy threshold for reads whose slices are
+copied in small chunks (the per-slice landing table then no longer applies).
 
 --writes prints the write side instead. A write starts at its first kernel
 (size_records) and ends where the next read's first slice copy is issued.
@@ -158,9 +164,21 @@ def busy(spans):
     return total
 
 
-def report(idx, slice_copies, ks, detail, split):
+def report(idx, slice_copies, ks, detail, split, before=None):
     t0 = slice_copies[0][0]
     last_copy = max(c[1] for c in slice_copies)
+    spans = sorted((c[0], c[1]) for c in slice_copies)
+    link = busy(spans)
+    gaps, end = [], spans[0][1]
+    for s, e in spans[1:]:
+        gaps.append(max(0.0, s - end))
+        end = max(end, e)
+    idle = f"{t0 - before:.3f}" if before is not None else "?"
+    print(f"read {idx}: link busy {link:.3f} of {last_copy - t0:.3f} ms "
+          f"({100 * link / (last_copy - t0):.0f}%), largest idle gap "
+          f"{max(gaps, default=0.0):.3f} ms, idle gaps over 0.05 ms sum "
+          f"{sum(g for g in gaps if g > 0.05):.3f} ms; first copy starts "
+          f"{idle} ms after the device's last activity before it")
     last_kernel = max((k[1] for k in ks), default=last_copy)
     after = [k for k in ks if k[1] > last_copy]
     print(f"read {idx}: {len(slice_copies)} slice copies, last lands at "
@@ -193,15 +211,19 @@ def report(idx, slice_copies, ks, detail, split):
 
 
 def main():
+    global SLICE_COPY_MS
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("out_dir")
     ap.add_argument("--read", type=int, default=-1,
                     help="read to print in detail (default: the last)")
     ap.add_argument("--whole-slices", action="store_true",
                     help="the run had TFREC_READ_SPLIT=0: one copy per slice")
+    ap.add_argument("--min-copy-ms", type=float, default=SLICE_COPY_MS,
+                    help="a copy longer than this is a slice (chunk) copy")
     ap.add_argument("--writes", action="store_true",
                     help="report the writes' head and end instead")
     args = ap.parse_args()
+    SLICE_COPY_MS = args.min_copy_ms
     kernels, copies = load(args.out_dir)
     dirs = {}
     for c in copies:
@@ -218,8 +240,10 @@ def main():
     if not reads:
         raise SystemExit("no slice copies found in the trace")
     detail = args.read % len(reads)
+    ends = sorted([k[1] for k in kernels] + [c[1] for c in copies])
     for i, (g, ks) in enumerate(reads):
-        report(i, g, ks, i == detail, not args.whole_slices)
+        before = max((e for e in ends if e <= g[0][0]), default=None)
+        report(i, g, ks, i == detail, not args.whole_slices, before)
 
 
 if __name__ == "__main__":

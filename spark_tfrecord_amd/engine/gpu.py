@@ -93,6 +93,23 @@ _READ_SLICE = int(os.environ.get("TFREC_READ_SLICE", 32 << 20))
 # link, so whole slices alternating between them land in pairs and the tail
 # holds a pair's work (9.18 ms); TFREC_READ_SPLIT=0 restores that.
 _SPLIT_SLICES = os.environ.get("TFREC_READ_SPLIT", "1") != "0"
+# Staged sliced read (the file's mapping cannot be registered): a native
+# thread stages the file into pinned memory chunk by chunk and enqueues each
+# chunk's copy at once (csrc/hip/stage_upload.hip). TFREC_STAGE_CHUNK is the
+# chunk size; a chunk of a whole slice or more is whole-slice staging, the
+# default: 8 MiB chunks start the first copy ~0.12 ms sooner but could not be
+# told from it over 10 alternating rounds (9.15 against 9.31 ms, spread 0.6).
+_STAGE_CHUNK = int(os.environ.get("TFREC_STAGE_CHUNK", 32 << 20))
+# TFREC_STAGE_SOURCE=map|pread: chunks come from the file's cached,
+# unregistered mapping (memcpy on the IO pool), or from pread() on the pool,
+# which is also what a file without a mapping gets.
+_STAGE_SOURCE = os.environ.get("TFREC_STAGE_SOURCE", "map").lower()
+if _STAGE_SOURCE not in ("map", "pread"):
+    raise ValueError(f"Unsupported TFREC_STAGE_SOURCE {_STAGE_SOURCE!r} "
+                     "(expected 'map' or 'pread')")
+# TFREC_FORCE_STAGED=1 takes the staged route for the sliced read even where
+# the mapping registers (to measure and test it on such a platform).
+_FORCE_STAGED = os.environ.get("TFREC_FORCE_STAGED", "0") != "0"
 _WRITE_SLICES = int(os.environ.get("TFREC_WRITE_SLICES", 8))
 # Where the file's mapping cannot be registered, the staged sliced write
 # copies its slices into the (unregistered) mapping with the IO pool instead
@@ -1210,30 +1227,45 @@ class _StreamedRead:
 
 
 class _SliceCopies:
-    """The H2D slices of one read on the side streams. `events` holds one
-    list of events per issued slice: the main stream gates each slice's work
-    on just that slice's copies. `ptr` is the file's registered mapping, or,
-    with `fd`, a pinned staging buffer of the file's size for a file whose
-    mapping cannot be registered: issue() then reads each slice from the
-    file into the buffer before it copies it."""
+    """The H2D slices of one read on the side streams; the main stream gates
+    each slice's work on just that slice's copies (gate_main). `ptr` is the
+    file's registered mapping, whose slices issue() enqueues and `events`
+    holds one list of events per issued slice for. With `fd`, `ptr` is a
+    pinned staging buffer of the file's size for a file whose mapping cannot
+    be registered: a native StagedUpload then owns a thread that stages the
+    file (from the unregistered mapping at `mapped`, or with pread) and
+    enqueues the copies by itself, and issue() only waits for it. close()
+    joins that thread; it must run before `fd` is closed."""
 
     def __init__(self, data: torch.Tensor, plan, ptr: int,
-                 fd: Optional[int] = None):
+                 fd: Optional[int] = None, mapped: int = 0):
         self.data, self.plan, self.ptr, self.fd = data, plan, ptr, fd
         self.events = []
+        self.upload = None
         main = torch.cuda.current_stream()
-        for st in _dma_streams():
+        streams = _dma_streams()
+        for st in streams:
             st.wait_stream(main)  # `data` allocation ordering
             data.record_stream(st)
+        if fd is not None:
+            # started after the waits above are on the side streams
+            self.upload = _native.StagedUpload(
+                fd, mapped if _STAGE_SOURCE == "map" else 0, ptr,
+                data.data_ptr(), [p.b0 for p in plan] + [plan[-1].b1],
+                streams[0].cuda_stream, streams[-1].cuda_stream,
+                max(1, _STAGE_CHUNK), _SPLIT_SLICES, data.device.index)
 
     def issue(self, upto: int):
-        """Issue the slices below `upto` that are not yet under way."""
+        """Make sure the slices below `upto` are issued: enqueue those not
+        yet under way, or (staged) wait until the upload thread has."""
+        upto = min(upto, len(self.plan))
+        if self.upload is not None:
+            if upto > 0:
+                self.upload.wait_issued(upto - 1)
+            return
         streams = _dma_streams()
-        for s in range(len(self.events), min(upto, len(self.plan))):
+        for s in range(len(self.events), upto):
             p = self.plan[s]
-            if self.fd is not None:
-                _native.pread_parallel(self.fd, self.ptr + p.b0, p.b1 - p.b0,
-                                       p.b0)
             # each slice goes half on either DMA stream: the streams share
             # the link, so whole slices alternating between them land in
             # PAIRS; split, slice k lands alone while k+1 is still in flight
@@ -1251,6 +1283,22 @@ class _SliceCopies:
                 evs.append(ev)
             self.events.append(evs)
 
+    def gate_main(self, s: int):
+        """The main stream waits for slice s's copies. Staged, the host first
+        waits until the upload thread has recorded the slice's events: a
+        stream told to wait on an event not yet recorded does not wait."""
+        if self.upload is not None:
+            for ev in self.upload.wait_issued(s):
+                _native.gpu_stream_wait_event(_stream(), ev)
+            return
+        main = torch.cuda.current_stream()
+        for ev in self.events[s]:
+            main.wait_event(ev)
+
+    def close(self):
+        if self.upload is not None:
+            self.upload.close()
+
 
 def _scan_blocks(p: stream_plan.SlicePlan) -> int:
     """Frame-scan blocks (== block_counts entries) of slice p's scan range."""
@@ -1259,12 +1307,12 @@ def _scan_blocks(p: stream_plan.SlicePlan) -> int:
     return int(_native.gpu_frame_scan_blocks(p.scan_lo, p.scan_hi))
 
 
-def _count_slice(data, p, evs, block_counts, base: int) -> int:
-    """Once slice p's copies (events evs) have landed: the COUNT pass over
-    its scan range into block_counts[base:]. Returns its block count."""
-    main = torch.cuda.current_stream()
-    for ev in evs:
-        main.wait_event(ev)
+def _count_slice(data, copies: _SliceCopies, s: int, block_counts,
+                 base: int) -> int:
+    """Once the copies of slice s have landed: the COUNT pass over its scan
+    range into block_counts[base:]. Returns its block count."""
+    copies.gate_main(s)
+    p = copies.plan[s]
     nb = _scan_blocks(p)
     if nb:
         _native.gpu_frame_scan_count(data.data_ptr(), data.numel(), p.scan_lo,
@@ -1283,8 +1331,8 @@ def _read_unstreamed(data, plan, block_counts, copies: _SliceCopies,
     last_read["path"] = "fallback" if _STREAM_DECODE else "unstreamed"
     copies.issue(len(plan))
     base = sum(_scan_blocks(p) for p in plan[:first])
-    for p, evs in zip(plan[first:], copies.events[first:]):
-        base += _count_slice(data, p, evs, block_counts, base)
+    for s in range(first, len(plan)):
+        base += _count_slice(data, copies, s, block_counts, base)
     ranges = [(p.scan_lo, p.scan_hi) for p in plan if p.scan_hi > p.scan_lo]
     off, lens, _ = _emit_and_chain(data, ranges, block_counts, data.numel())
     return decode_device(data, off, lens, schema, record_type, verify_crc)
@@ -1304,8 +1352,10 @@ def read_file_to_batch_pipelined(path: str, schema: StructType, record_type: str
     the streamed attempt for _read_unstreamed, which is also what
     TFREC_STREAM_DECODE=0 runs. The slices come from the file's registered
     mapping, all issued up front. Where the mapping cannot be registered
-    they come through pinned staging, each one read from the file while its
-    predecessor is copied and the one before that is decoded."""
+    they come through pinned staging: a native thread stages the file chunk
+    by chunk and enqueues each chunk's copy at once, independent of this
+    thread, which only waits for a slice to be issued before it gates that
+    slice's kernels on its copies."""
     check_native()
     n = os.path.getsize(path)
     if n == 0:
@@ -1313,7 +1363,7 @@ def read_file_to_batch_pipelined(path: str, schema: StructType, record_type: str
         return decode_device(torch.zeros(0, dtype=torch.uint8, device=device),
                              z, z.clone(), schema, record_type, verify_crc)
     ptr, pinned = _native.file_mmap_pinned(path, n, False)
-    if pinned:
+    if pinned and not _FORCE_STAGED:
         return _read_sliced(n, ptr, None, schema, record_type, verify_crc,
                             device)
     for st in _dma_streams():
@@ -1322,23 +1372,37 @@ def read_file_to_batch_pipelined(path: str, schema: StructType, record_type: str
     fd = os.open(path, os.O_RDONLY)
     try:
         return _read_sliced(n, stage.data_ptr(), fd, schema, record_type,
-                            verify_crc, device)
+                            verify_crc, device, mapped=ptr)
     finally:
         os.close(fd)
 
 
 def _read_sliced(n: int, ptr: int, fd: Optional[int], schema: StructType,
-                 record_type: str, verify_crc: bool, device) -> RecordBatch:
+                 record_type: str, verify_crc: bool, device,
+                 mapped: int = 0) -> RecordBatch:
     """read_file_to_batch_pipelined over the n bytes at `ptr` (fd is None),
-    or over those of file `fd` staged through the pinned buffer at `ptr`."""
+    or over those of file `fd` staged through the pinned buffer at `ptr`
+    (from its unregistered mapping at `mapped`, if it has one)."""
     data = torch.empty(n, dtype=torch.uint8, device=device)
     plan = stream_plan.plan_slices(n, _READ_SLICE)
     S = len(plan)
     # pre-size the per-block count buffer over the slice scan ranges
     block_counts = torch.empty(max(sum(_scan_blocks(p) for p in plan), 1),
                                dtype=torch.int64, device=data.device)
-    copies = _SliceCopies(data, plan, ptr, fd)
-    copies.issue(S if fd is None else 1)
+    copies = _SliceCopies(data, plan, ptr, fd, mapped)
+    try:
+        return _decode_slices(data, plan, block_counts, copies, schema,
+                              record_type, verify_crc)
+    finally:
+        copies.close()  # joins the upload thread before fd is closed
+
+
+def _decode_slices(data, plan, block_counts, copies: _SliceCopies,
+                   schema: StructType, record_type: str,
+                   verify_crc: bool) -> RecordBatch:
+    S = len(plan)
+    if copies.upload is None:
+        copies.issue(S)
     last_read.update(path="streamed", slices=S, regrows=0, host_waits=0)
     unstreamed = (data, plan, block_counts, copies)
     decode = (schema, record_type, verify_crc)
@@ -1348,10 +1412,9 @@ def _read_sliced(n: int, ptr: int, fd: Optional[int], schema: StructType,
     rd = _StreamedRead(data, S, *decode)
     base = 0  # block_counts offset of the current slice
     for s, p in enumerate(plan):
-        nb = _count_slice(data, p, copies.events[s], block_counts, base)
-        # staged: the host reads slice s + 1 here, under slice s's copy and
-        # COUNT and slice s - 1's kernels, before step() blocks on them
-        copies.issue(s + 2)
+        # staged: blocks (GIL released) until the upload thread has issued
+        # slice s; the thread stages and copies the later slices meanwhile
+        nb = _count_slice(data, copies, s, block_counts, base)
         counts = block_counts[base:base + nb] if nb else None
         base += nb
         if not rd.step(p, counts, last=s == S - 1):
