@@ -1004,7 +1004,10 @@ __global__ void frame_scan_pass_kernel(const u8* __restrict__ data, i64 N,
   __shared__ uint32_t tab[8][256];
   __shared__ unsigned int cnt[256];
   stage_crc_tables(tab);
-  const u64* wdata = reinterpret_cast<const u64*>(data);  // data is 8B-aligned
+  // data is 8B-aligned: every caller (scan_frames_device from reader.py,
+  // validate.py, torch_data.py and gpu.py; the sliced read) hands over the
+  // start of a fresh device allocation, never a view into one at an offset.
+  const u64* wdata = reinterpret_cast<const u64*>(data);
   i64 c_lo = pos_start / kPosPerLane;
   i64 c_hi = (pos_end + kPosPerLane - 1) / kPosPerLane;
   i64 c = c_lo + (i64)blockIdx.x * blockDim.x + threadIdx.x;

@@ -182,10 +182,38 @@ def _multi_dma(dst: int, src: int, n: int, fn, after_main: bool):
             streams[i].synchronize()
 
 
+def _half_events(tag: str, chunk: int, device) -> list:
+    """The two events that guard the halves [0, chunk) and [chunk, 2*chunk)
+    of pinned_buffer(tag), kept beside the buffer in the thread's pool: each
+    is recorded behind the last async copy out of its half, and whoever
+    refills a half waits for it first. They outlive a call, because the
+    copies do: the caller of a staged read goes on to the next file while
+    the stream may not yet have run this one's copies. Events of another
+    chunk size or device are waited out and replaced: their halves lie
+    elsewhere."""
+    guards = getattr(_pinned_tls, "guards", None)
+    if guards is None:
+        guards = _pinned_tls.guards = {}
+    key = (chunk, device.index)
+    st = guards.get(tag)
+    if st is None or st[0] != key:
+        if st is not None:
+            for e in st[1]:
+                e.synchronize()
+        st = guards[tag] = (key, [torch.cuda.Event(), torch.cuda.Event()])
+    return st[1]
+
+
 def _read_file_staged(path: str, dev: torch.Tensor) -> torch.Tensor:
+    """File -> `dev` through the two halves of the thread's "fread" pinned
+    buffer. The copies are only enqueued: back-to-back calls (_upload_files)
+    share the buffer, so the events that say a half's copy has run are the
+    pool's (_half_events), not this call's. With events of its own, a call
+    found them unrecorded, refilled half 0 at once, and the previous file's
+    queued copy then delivered this file's bytes into that file's slice."""
     n = dev.numel()
     buf = pinned_buffer("fread", min(n, 2 * _CHUNK) or 1)
-    ev = [torch.cuda.Event(), torch.cuda.Event()]
+    ev = _half_events("fread", _CHUNK, dev.device)
     fd = os.open(path, os.O_RDONLY)
     try:
         pos = 0
@@ -382,7 +410,11 @@ def scan_frames_device(data: torch.Tensor):
     (two-pass count/emit — candidates come out position-sorted by
     construction, no device sort); the chain pos[k+1] == pos[k]+16+len[k]
     must hold exactly — a false positive (p=2^-32/byte) or a torn file
-    breaks it and raises."""
+    breaks it and raises.
+
+    `data` must start 8-byte aligned (the kernel loads it as u64 words).
+    Every caller passes the start of a fresh allocation, so there is no
+    copy for views at an odd offset here."""
     check_native()
     N = data.numel()
     device = data.device
