@@ -624,6 +624,60 @@ def _torch_ragged(batch, lo, hi, torch):
     return out
 
 
+FRAMES_STL = (16, 1, 128)  # Padded3D shape of the frames column
+
+
+def _frames_shard(R, torch):
+    """A decoded shard of R rows of one bytes FeatureList, built in its wire
+    form on the device: 0..16 steps per row (uniform), one 128-byte string
+    per step."""
+    import spark_tfrecord_amd as stf
+    from spark_tfrecord_amd.columnar import RecordBatch, WireColumn
+    from spark_tfrecord_amd.schema import KIND_BYTES
+
+    S, _, L = FRAMES_STL
+    g = torch.Generator(device="cuda").manual_seed(5)
+    ns = torch.randint(0, S + 1, (R,), device="cuda", generator=g)
+    list_off = torch.zeros(R + 1, dtype=torch.int64, device="cuda")
+    list_off[1:] = ns.cumsum(0)
+    N = int(list_off[-1])
+    sub_off = torch.arange(N + 1, dtype=torch.int64, device="cuda")
+    values = torch.randint(1, 256, (N * L,), device="cuda", generator=g,
+                           dtype=torch.uint8)
+    col = WireColumn(KIND_BYTES, True,
+                     torch.ones(R, dtype=torch.uint8, device="cuda"),
+                     list_off.clone(), values, elem_off=sub_off * L,
+                     list_off=list_off, sub_off=sub_off)
+    schema = stf.StructType([stf.StructField(
+        "frames", stf.ArrayType(stf.ArrayType(stf.BinaryType())), True)])
+    return RecordBatch(schema, [col], R)
+
+
+def _torch_frames(batch, lo, hi, torch):
+    """Padded3D(16, 1, 128) for rows [lo, hi) of a frames shard in torch
+    indexing ops, no host wait: the comparison for collate_cells3d_kernel."""
+    S, T, L = FRAMES_STL
+    col = batch.column("frames")
+    dev = col.values.device
+    l0 = col.list_off[lo:hi]
+    ns = col.list_off[lo + 1:hi + 1] - l0
+    s = torch.arange(S, device=dev)
+    step = (l0[:, None] + s).clamp_(max=col.sub_off.numel() - 2)
+    e0 = col.sub_off[step]
+    ne = torch.where(s < ns[:, None], col.sub_off[step + 1] - e0, 0)
+    t = torch.arange(T, device=dev)
+    item = (e0[..., None] + t).clamp_(max=col.elem_off.numel() - 2)
+    v0 = col.elem_off[item]
+    ln = torch.where(t < ne[..., None], col.elem_off[item + 1] - v0, 0)
+    j = torch.arange(L, device=dev)
+    idx = (v0[..., None] + j).clamp_(max=col.values.numel() - 1)
+    return {"frames": torch.where(j < ln[..., None], col.values[idx], 0),
+            "frames_steps": ns.clamp(max=S).int(),
+            "frames_outer": ne.clamp(max=T).int(),
+            "frames_len": ln.clamp(max=L).int(),
+            "_bad": (ns > S).any() | (ne > T).any() | (ln > L).any()}
+
+
 def bench_collate(args):
     """--rows flagship Example rows in 8 shards, batches of 8192. Whole
     pipelines, alternating after a warm-up of each: (a) the ragged
@@ -632,9 +686,12 @@ def bench_collate(args):
     alone over one decoded
     shard: (k) collate_rows_kernel through Collator.run, (d) the same four
     columns in torch indexing ops, (rk) the four columns packed (Ragged /
-    Ragged2D) through Collator.run, (rd) those in torch ops. --collate-part
-    kernel|torch|ragged|ragged_torch runs only that loop, for a kernel trace
-    of its own; none only decodes the shard."""
+    Ragged2D) through Collator.run, (rd) those in torch ops, (f) a bytes
+    FeatureList of as many rows (0..16 steps of one 128-byte string each) as
+    Padded3D(16, 1, 128) through Collator.run, (fd) that in torch ops.
+    --collate-part kernel|torch|ragged|ragged_torch|frames|frames_torch runs
+    only that loop, for a kernel trace of its own; none only decodes the
+    shard."""
     import torch
 
     import spark_tfrecord_amd as stf
@@ -701,8 +758,30 @@ def bench_collate(args):
             outs = _torch_ragged(shard, lo, hi, torch)
         return outs
 
+    # a bytes FeatureList (_frames_shard) as Padded3D, and in torch ops
+    co_f = frames = None
+    if part in ("all", "frames", "frames_torch"):
+        from spark_tfrecord_amd.torch_data import Padded3D
+        frames = _frames_shard(R, torch)
+        co_f = Collator(frames.schema, {"frames": Padded3D(*FRAMES_STL)},
+                        "gpu")
+        co_f.set_window([frames])
+
+    def run_frames():
+        for slot, row in sels:
+            outs, status = co_f.run(slot, row)
+        assert status[0] == (1 << 64) - 1
+        return outs
+
+    def run_frames_torch():
+        for lo, hi in ranges:
+            outs = _torch_frames(frames, lo, hi, torch)
+        assert not bool(outs["_bad"])
+        return outs
+
     alone = {"kernel": run_kernel, "torch": run_torch,
-             "ragged": run_ragged, "ragged_torch": run_ragged_torch}
+             "ragged": run_ragged, "ragged_torch": run_ragged_torch,
+             "frames": run_frames, "frames_torch": run_frames_torch}
     if part != "all":
         alone = {k: f for k, f in alone.items() if k == part}
     if part == "all":
@@ -712,8 +791,11 @@ def bench_collate(args):
         a, b = run_ragged(), run_ragged_torch()
         for k in b:  # and the packed ones, up to the batch's totals
             assert torch.equal(a[k][:b[k].numel()], b[k]), k
+        a, b = run_frames(), run_frames_torch()
+        for k in a:
+            assert torch.equal(a[k], b[k]), k
 
-    colls = {"kernel": co, "ragged": co_r}
+    colls = {"kernel": co, "ragged": co_r, "frames": co_f}
 
     def nbytes(outs):
         return sum(t.numel() * t.element_size() for k, t in outs.items()
@@ -809,7 +891,8 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--collate-part", default="all",
                     choices=["all", "kernel", "torch", "ragged",
-                             "ragged_torch", "none"],
+                             "ragged_torch", "frames", "frames_torch",
+                             "none"],
                     help="collate: run only one collation-alone loop "
                          "(for a kernel trace of its own)")
     args = ap.parse_args()

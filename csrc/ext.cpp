@@ -748,7 +748,8 @@ py::bytes host_snap_chunk(py::buffer data) {
 }
 
 // Host run of the batch collation core shared with the gfx950 kernel
-// (csrc/collate_core.h): the same do_unit over every unit of every column,
+// (csrc/collate_core.h): the same do_unit (unit3d for the three-level dense
+// columns, host_ragged for the packed ones) over every unit of every column,
 // in plain loops. The tables hold host addresses of numpy buffers the caller
 // keeps alive; geometry is checked by the caller (collate.py), as for the
 // kernel. This is the CPU engine's collation, not only a test hook.
@@ -763,7 +764,7 @@ void host_collate(py::array_t<i64, py::array::c_style> src,
   const i64 ncols = cols.size() / cl::kColWords;
   const i64 B = sel_slot.size();
   if (ncols <= 0 || ncols > cl::kMaxCols || cols.size() % cl::kColWords)
-    throw std::invalid_argument("host_collate: 1..64 columns of 16 words");
+    throw std::invalid_argument("host_collate: 1..64 columns of 20 words");
   if (sel_row.size() != B || status.size() != 2 ||
       src.size() % (ncols * cl::kSrcWords))
     throw std::invalid_argument("host_collate: table sizes disagree");

@@ -13,6 +13,11 @@ FixedLenFeature / VarLenFeature), and `collate_batch` gathers B rows, each a
     Padded2D(max_outer, max_inner, pad=0, truncate=False)
                                           name: [B, T, L], name_outer: int32
                                           [B], name_len: int32 [B, T]
+    Padded3D(max_steps, max_items, max_bytes, pad=0, truncate=False)
+                                          a FeatureList of bytes; name: uint8
+                                          [B, S, T, L], name_steps: int32 [B],
+                                          name_outer: int32 [B, S], name_len:
+                                          int32 [B, S, T]
 
 or which packed form, values plus `cu_seqlens`-style offsets, with shapes
 fixed by the spec (so `out=` tensors and graph capture keep working):
@@ -24,13 +29,22 @@ fixed by the spec (so `out=` tensors and graph capture keep working):
                                           name_item_offsets: int32
                                           [item_capacity+1], name_offsets:
                                           int32 [B+1] (over items)
+    Ragged3D(step_capacity, item_capacity, value_capacity)
+                                          a FeatureList of bytes; name: uint8
+                                          [value_capacity], name_item_offsets:
+                                          int32 [item_capacity+1] (into the
+                                          bytes), name_step_offsets: int32
+                                          [step_capacity+1] (into the
+                                          strings), name_offsets: int32 [B+1]
+                                          (over steps)
 
 Every spec takes `dtype="int32"` on an int64 column: the kernel narrows, and
 a value outside int32 is a RANGE error.
 
 The semantics are csrc/collate_core.h's, run by the gfx950 kernels
-(csrc/hip/collate.hip: one launch for the dense columns, two more for all
-packed ones, one host wait per batch) or by the same core in host loops
+(csrc/hip/collate.hip: one launch for the dense columns, one more for all
+Padded3D columns, two more for all packed ones, one host wait per batch) or
+by the same core in host loops
 (`_native.host_collate`).
 """
 
@@ -48,10 +62,11 @@ from .columnar import RecordBatch, wire_fields
 from .schema import (KIND_BYTES, KIND_FLOAT, KIND_INT64, NullType, StructType,
                      is_sequence_field, wire_kind_of)
 
-__all__ = ["FixedLen", "Padded", "Padded2D", "Ragged", "Ragged2D", "Collator",
-           "collate_batch", "plan_columns", "CAUSES"]
+__all__ = ["FixedLen", "Padded", "Padded2D", "Padded3D", "Ragged", "Ragged2D",
+           "Ragged3D", "Collator", "collate_batch", "plan_columns", "CAUSES"]
 
 CM_FIXED, CM_PADDED, CM_PADDED2D, CM_RAGGED, CM_RAGGED2D = 0, 1, 2, 3, 4
+CM_RAGGED3D, CM_PADDED3D = 5, 6
 CC_MISSING, CC_LENGTH, CC_RANGE, CC_CAPACITY = 1, 2, 3, 4
 CAUSES = {CC_MISSING: "MISSING (row absent or empty and the spec has no "
                       "default)",
@@ -99,6 +114,19 @@ class Padded2D:
 
 
 @dataclass(frozen=True)
+class Padded3D:
+    """A FeatureList of bytes: up to `max_steps` steps of up to `max_items`
+    strings of up to `max_bytes` bytes each, the Padded rule at every level.
+    `dtype` must stay None."""
+    max_steps: int
+    max_items: int
+    max_bytes: int
+    pad: int = 0
+    truncate: bool = False
+    dtype: Optional[str] = None
+
+
+@dataclass(frozen=True)
 class Ragged:
     """The rows' values back to back in `capacity` elements (zero past the
     batch's total) and int32 offsets `[B+1]`. `max_len` cuts each row to its
@@ -115,6 +143,18 @@ class Ragged2D:
     """The rows' items (strings of a bytes column, lists of a FeatureList)
     back to back: values `[value_capacity]`, int32 item offsets
     `[item_capacity+1]` into them, int32 row offsets `[B+1]` into the items."""
+    item_capacity: int
+    value_capacity: int
+    dtype: Optional[str] = None
+
+
+@dataclass(frozen=True)
+class Ragged3D:
+    """A FeatureList of bytes, packed: the bytes back to back in
+    `value_capacity`, int32 item offsets `[item_capacity+1]` into them (one
+    per string), int32 step offsets `[step_capacity+1]` into the strings,
+    int32 row offsets `[B+1]` into the steps. `dtype` must stay None."""
+    step_capacity: int
     item_capacity: int
     value_capacity: int
     dtype: Optional[str] = None
@@ -156,11 +196,18 @@ class _Plan:
     squeeze: bool   # FixedLen(length=None): output [B], not [B, 1]
     narrow: bool = False  # dtype="int32": int64 values stored as int32
     cap: int = 0    # Ragged*: value capacity (0: B * L)
-    icap: int = 0   # Ragged2D: item capacity
+    icap: int = 0   # Ragged2D/3D: item capacity
+    S: int = 1      # Padded3D: max steps
+    scap: int = 0   # Ragged3D: step capacity
 
     @property
     def ragged(self) -> bool:
-        return self.mode >= CM_RAGGED
+        return CM_RAGGED <= self.mode <= CM_RAGGED3D
+
+    @property
+    def levels(self) -> int:
+        """Raw offset arrays a ragged column keeps in the scratch."""
+        return {CM_RAGGED: 1, CM_RAGGED2D: 2, CM_RAGGED3D: 3}[self.mode]
 
     def capacity(self, B: int) -> int:
         return self.cap or B * self.L
@@ -175,6 +222,16 @@ class _Plan:
             return {self.name: ((self.cap,), dt),
                     self.name + "_item_offsets": ((self.icap + 1,), np.int32),
                     self.name + "_offsets": ((B + 1,), np.int32)}
+        if self.mode == CM_RAGGED3D:
+            return {self.name: ((self.cap,), dt),
+                    self.name + "_item_offsets": ((self.icap + 1,), np.int32),
+                    self.name + "_step_offsets": ((self.scap + 1,), np.int32),
+                    self.name + "_offsets": ((B + 1,), np.int32)}
+        if self.mode == CM_PADDED3D:
+            return {self.name: ((B, self.S, self.T, self.L), dt),
+                    self.name + "_steps": ((B,), np.int32),
+                    self.name + "_outer": ((B, self.S), np.int32),
+                    self.name + "_len": ((B, self.S, self.T), np.int32)}
         if self.mode == CM_FIXED:
             return {self.name: ((B,) if self.squeeze else (B, self.L), dt)}
         if self.mode == CM_PADDED:
@@ -290,9 +347,31 @@ def plan_columns(schema: StructType, features: Dict[str, Any]) -> List[_Plan]:
                 _positive(spec.max_inner, "max_inner", name),
                 _fill_bits(kind, spec.pad, name, nar),
                 (CF_TRUNCATE if spec.truncate else 0) | by, False, nar))
+        elif isinstance(spec, (Padded3D, Ragged3D)):
+            if not (seq and kind == KIND_BYTES):
+                raise ValueError(
+                    f"column '{name}': {type(spec).__name__} takes a bytes "
+                    f"FeatureList, not {f.dataType.simple_string()}")
+            _narrow(spec, kind, name)  # a bytes column takes no dtype
+            if isinstance(spec, Ragged3D):
+                plans.append(_Plan(
+                    name, by_name[name], kind, CM_RAGGED3D, 1, 1, 0, CF_BYTES,
+                    False, False,
+                    _capacity(spec.value_capacity, "value_capacity", name),
+                    _capacity(spec.item_capacity, "item_capacity", name),
+                    1, _capacity(spec.step_capacity, "step_capacity", name)))
+                continue
+            plans.append(_Plan(
+                name, by_name[name], kind, CM_PADDED3D,
+                _positive(spec.max_items, "max_items", name),
+                _positive(spec.max_bytes, "max_bytes", name),
+                _fill_bits(kind, spec.pad, name),
+                (CF_TRUNCATE if spec.truncate else 0) | CF_BYTES, False,
+                False, 0, 0, _positive(spec.max_steps, "max_steps", name)))
         else:
             raise ValueError(f"column '{name}': {spec!r} is not a FixedLen, "
-                             f"Padded, Padded2D, Ragged or Ragged2D spec")
+                             f"Padded, Padded2D, Padded3D, Ragged, Ragged2D "
+                             f"or Ragged3D spec")
     return plans
 
 
@@ -408,8 +487,11 @@ class Collator:
                 if p.capacity(B) >= 1 << 31:
                     raise ValueError(f"column '{p.name}': {p.capacity(B)} "
                                      f"elements do not fit one batch (2^31)")
-            elif B * p.T * p.L >= 1 << 31:
-                raise ValueError(f"column '{p.name}': {B}x{p.T}x{p.L} "
+            elif B * p.S * p.T * p.L >= 1 << 31:
+                shape = "x".join(map(str, (B, p.S, p.T, p.L)
+                                     if p.mode == CM_PADDED3D
+                                     else (B, p.T, p.L)))
+                raise ValueError(f"column '{p.name}': {shape} "
                                  f"elements do not fit one batch (2^31)")
         return sel_slot.astype(np.int32), sel_row.astype(np.int64), B
 
@@ -441,14 +523,13 @@ class Collator:
 
     def _scratch_words(self, B: int) -> int:
         """Raw 64-bit offsets of the ragged columns: [B+1] per level."""
-        return sum((B + 1) * (2 if p.mode == CM_RAGGED2D else 1)
-                   for p in self.plans if p.ragged)
+        return sum((B + 1) * p.levels for p in self.plans if p.ragged)
 
     def _col_table(self, B: int, outs: dict, scratch: int):
-        """-> (table, dense tiles, ragged columns, ragged tiles); `scratch`
-        is the address of `_scratch_words(B)` words."""
+        """-> (table, dense tiles, ragged columns, ragged tiles, Padded3D
+        tiles); `scratch` is the address of `_scratch_words(B)` words."""
         table = np.zeros((len(self.plans), _COL_WORDS), np.uint64)
-        tile0 = rtile0 = nragged = 0
+        tile0 = rtile0 = ctile0 = nragged = 0
         for c, p in enumerate(self.plans):
             esize = _ESIZE[p.kind]
             osize = 4 if p.narrow else esize
@@ -456,28 +537,41 @@ class Collator:
                 cap = p.capacity(B)
                 units = (cap + 7) // 8 if esize == 1 else cap
                 io = outs.get(p.name + "_item_offsets")
+                so = outs.get(p.name + "_step_offsets")
                 if io is not None:
                     units = max(units, p.icap + 1)
+                if so is not None:
+                    units = max(units, p.scap + 1)
                 table[c] = [p.mode, esize, 1, p.L, 0, p.flags,
                             outs[p.name].data_ptr(),
                             outs[p.name + "_offsets"].data_ptr(),
                             io.data_ptr() if io is not None else 0,
-                            tile0, units, osize, scratch, cap, p.icap, rtile0]
-                scratch += 8 * (B + 1) * (2 if io is not None else 1)
+                            tile0, units, osize, scratch, cap, p.icap, rtile0,
+                            1, so.data_ptr() if so is not None else 0,
+                            p.scap, ctile0]
+                scratch += 8 * (B + 1) * p.levels
                 rtile0 += (units + _TILE_UNITS - 1) // _TILE_UNITS
                 nragged += 1
                 continue
-            elems = B * p.T * p.L
+            elems = B * p.S * p.T * p.L
             units = (elems + 7) // 8 if esize == 1 else elems
             ln = outs.get(p.name + "_len")
             outer = outs.get(p.name + "_outer")
+            steps = outs.get(p.name + "_steps")
             table[c] = [p.mode, esize, p.T, p.L, p.fill, p.flags,
                         outs[p.name].data_ptr(),
                         ln.data_ptr() if ln is not None else 0,
                         outer.data_ptr() if outer is not None else 0,
-                        tile0, units, osize, 0, 0, 0, rtile0]
-            tile0 += (units + _TILE_UNITS - 1) // _TILE_UNITS
-        return table.view(np.int64).reshape(-1), tile0, nragged, rtile0
+                        tile0, units, osize, 0, 0, 0, rtile0,
+                        p.S, steps.data_ptr() if steps is not None else 0,
+                        0, ctile0]
+            tiles = (units + _TILE_UNITS - 1) // _TILE_UNITS
+            if p.mode == CM_PADDED3D:
+                ctile0 += tiles
+            else:
+                tile0 += tiles
+        return (table.view(np.int64).reshape(-1), tile0, nragged, rtile0,
+                ctile0)
 
     # -- one batch ----------------------------------------------------------
     def launch(self, sel_slot, sel_row, out: Optional[dict] = None):
@@ -504,7 +598,7 @@ class Collator:
             self._scratch = torch.empty(nscratch, dtype=torch.int64,
                                         device="cuda")
         scratch = self._scratch if nscratch else None
-        cols, ntiles, nragged, rtiles = self._col_table(
+        cols, ntiles, nragged, rtiles, ctiles = self._col_table(
             B, outs, scratch.data_ptr() if nscratch else 0)
         # one upload: status init | sel_row | column table | sel_slot
         nc = cols.size
@@ -523,6 +617,10 @@ class Collator:
         if ntiles:
             _native.gpu_collate_rows(*tables, ntiles, base,
                                      stream.cuda_stream)
+            self.launches += 1
+        if ctiles:
+            _native.gpu_collate_cells3d(*tables, ctiles, base,
+                                        stream.cuda_stream)
             self.launches += 1
         if nragged:
             _native.gpu_collate_ragged(*tables, nragged, rtiles, base,

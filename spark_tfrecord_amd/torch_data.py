@@ -13,8 +13,9 @@ torch.distributed ranks and DataLoader workers round-robin.
 
 TFRecordBatchDataset goes the rest of the way: shuffled batches of a fixed
 size, dense or packed (values + offsets), collated on the device from a
-window of decoded shards (collate.py; one kernel launch per batch, two more
-when it has packed columns, and one host wait).
+window of decoded shards (collate.py; one kernel launch per batch, one more
+when it has Padded3D columns, two more when it has packed columns, and one
+host wait).
 
     ds = TFRecordBatchDataset(path, features={"id": FixedLen(),
                                               "ints": Padded(8)},
@@ -41,10 +42,10 @@ from .io import paths as P
 from .schema import KIND_BYTES, StructType
 from .columnar import RecordBatch
 from .collate import (STATUS_CLEAN, Collator, FixedLen, Padded, Padded2D,
-                      Ragged, Ragged2D, plan_columns)
+                      Padded3D, Ragged, Ragged2D, Ragged3D, plan_columns)
 
 __all__ = ["TFRecordIterableDataset", "TFRecordBatchDataset", "FixedLen",
-           "Padded", "Padded2D", "Ragged", "Ragged2D"]
+           "Padded", "Padded2D", "Padded3D", "Ragged", "Ragged2D", "Ragged3D"]
 
 
 def _as_torch(x, device):
@@ -288,8 +289,8 @@ class _Slot:
 class TFRecordBatchDataset(_ShardSource):
     """Batches of exactly `batch_size` rows, shuffled through a window of
     decoded shards and collated per `features` (name -> FixedLen / Padded /
-    Padded2D for dense tensors, Ragged / Ragged2D for values + offsets, see
-    collate.py).
+    Padded2D / Padded3D for dense tensors, Ragged / Ragged2D / Ragged3D for
+    values + offsets, see collate.py).
 
     The window holds up to `shuffle_window` decoded shards; each has a
     seeded permutation of its rows. A batch draws `batch_size` rows
@@ -303,7 +304,8 @@ class TFRecordBatchDataset(_ShardSource):
 
     engine "gpu": shards decode on the device and stay there; per batch only
     the selection crosses the link, one kernel gathers every dense column
-    (two more launches cover all packed columns), and the iterator waits
+    (one more launch covers all Padded3D columns, two more all packed
+    columns), and the iterator waits
     once, on the status words. `truncated_rows` accumulates
     over an iteration; `last_stats` holds the last iteration's batches,
     kernel launches and host waits.
