@@ -19,6 +19,9 @@ driver runs it). This suite covers the rest, each printing one JSON line:
                   level 6, no segment table): host zlib pool vs the
                   speculative device inflater (foreign_gzip="host" |
                   "device"), as one file and as 32 files
+  lz4             GPU-engine read of lz4 flagship rows: the device LZ4
+                  decoder vs TFREC_LZ4=host vs the device Snappy decoder on
+                  the same rows as snappy, with each mode's spread
   snappy_write    GPU-engine snappy write of flagship rows, pyarrow's Snappy
                   on the host vs the device compressor (snappy_engine="host"
                   | "device"), as 1 shard and as 8 shards
@@ -493,6 +496,79 @@ def bench_snappy(args):
     shutil.rmtree(d, ignore_errors=True)
 
 
+def bench_lz4(args):
+    """GPU-engine read of --rows flagship Example rows written once with
+    codec="lz4" (8 shards): the device LZ4 decoder against TFREC_LZ4=host
+    (the same core on the CPU), and against the same rows as snappy through
+    the device Snappy decoder. The three alternate in one process after a
+    warm-up; every mode's fastest and slowest read are reported with its
+    mean, as the run-to-run spread."""
+    import torch
+
+    import spark_tfrecord_amd as stf
+    from spark_tfrecord_amd.engine import gpu as gpu_engine
+    from spark_tfrecord_amd.io import paths as P
+
+    rank, world = _env_world()
+    if not torch.cuda.is_available():
+        raise SystemExit("lz4 needs the GPU engine")
+    rows = args.rows
+    d = _workdir("lz4", rank)
+    table = _flagship_table(rows, 5 + rank)
+    dirs = {}
+    sizes = {}
+    for codec in ("lz4", "snappy"):
+        dirs[codec] = os.path.join(d, codec)
+        stf.write_tfrecord(table, dirs[codec], record_type="Example",
+                           codec=codec, num_shards=8, engine="gpu")
+        sizes[codec] = sum(os.path.getsize(f)
+                           for f in P.list_data_files(dirs[codec]))
+    schema = stf.read_tfrecord(dirs["lz4"], engine="gpu").schema
+    del table
+    modes = {"lz4 device": ("lz4", "device"), "lz4 host": ("lz4", "host"),
+             "snappy device": ("snappy", "device")}
+
+    def read(mode):
+        codec, knob = modes[mode]
+        os.environ["TFREC_LZ4"] = knob
+        del gpu_engine.last_lz4[:]
+        df = stf.read_tfrecord(dirs[codec], schema=schema, engine="gpu")
+        torch.cuda.synchronize()
+        assert bool(gpu_engine.last_lz4) == (mode == "lz4 device")
+        return df
+
+    times = {mode: [] for mode in modes}
+    blocks = 0
+    for mode in modes:
+        assert read(mode).count() == rows  # warm-up
+    for _ in range(args.reps):
+        for mode in modes:
+            t0 = time.perf_counter()
+            read(mode)
+            times[mode].append(time.perf_counter() - t0)
+            if mode == "lz4 device":
+                blocks = sum(e[1] for e in gpu_engine.last_lz4)
+    os.environ.pop("TFREC_LZ4", None)
+    mean = {mode: sum(t) / len(t) for mode, t in times.items()}
+    for mode, t in times.items():
+        codec = modes[mode][0]
+        _emit(rank, f"rows/sec read {mode}", rows / mean[mode], "rows/s",
+              {"rows": rows, "files": 8, "mode": mode,
+               "file_bytes": sizes[codec],
+               "ms_mean": round(mean[mode] * 1e3, 2),
+               "ms_min": round(min(t) * 1e3, 2),
+               "ms_max": round(max(t) * 1e3, 2),
+               "lz4_over_snappy_bytes": round(
+                   sizes["lz4"] / sizes["snappy"], 3),
+               "lz4_blocks": blocks if mode == "lz4 device" else None,
+               "device_over_host": round(
+                   mean["lz4 host"] / mean["lz4 device"], 3),
+               "device_lz4_over_device_snappy": round(
+                   mean["snappy device"] / mean["lz4 device"], 3),
+               "engine": "gpu", "reps": args.reps}, sum(t), 1)
+    shutil.rmtree(d, ignore_errors=True)
+
+
 def bench_snappy_write(args):
     """GPU-engine snappy write of --rows flagship Example rows: pyarrow's
     Snappy on the host (the default) against the device compressor, same
@@ -880,7 +956,7 @@ BENCHES = {"plumbing": bench_plumbing, "partitionby": bench_partitionby,
            "infer": bench_infer, "gzip_bytearray": bench_gzip_bytearray,
            "gzip_write": bench_gzip_write,
            "gzip_foreign": bench_gzip_foreign,
-           "snappy": bench_snappy, "snappy_write": bench_snappy_write,
+           "snappy": bench_snappy, "lz4": bench_lz4, "snappy_write": bench_snappy_write,
            "collate": bench_collate}
 
 

@@ -21,6 +21,7 @@ SOURCES = [ROOT / "csrc" / "ext.cpp", ROOT / "csrc" / "hip" / "kernels.hip",
            ROOT / "csrc" / "hip" / "inflate_foreign.hip",
            ROOT / "csrc" / "hip" / "snappy.hip",
            ROOT / "csrc" / "hip" / "snappy_enc.hip",
+           ROOT / "csrc" / "hip" / "lz4.hip",
            ROOT / "csrc" / "hip" / "collate.hip",
            ROOT / "csrc" / "hip" / "stage_upload.hip"]
 HEADERS = list((ROOT / "csrc").rglob("*.h"))

@@ -32,6 +32,7 @@
 #include "deflate_core.h"
 #include "inflate_core.h"
 #include "inflate_spec_core.h"
+#include "lz4_core.h"
 #include "snappy_core.h"
 #include "snappy_enc_core.h"
 #include "collate_core.h"
@@ -728,6 +729,32 @@ py::bytes host_unsnap_chunk(py::buffer comp, i64 expect_len) {
   return py::bytes(out);
 }
 
+// Host run of the raw LZ4 block decoder core shared with the gfx950 kernel
+// (csrc/lz4_core.h), serial: reading the input in place, or with `window`
+// through the kernel's staging window, which gives the same bytes. This is
+// the CPU engine's `.lz4` decoder, not only a test hook. The output stands
+// between guard bytes that the core must leave alone.
+py::bytes host_unlz4_block(py::buffer comp, i64 cap, bool window) {
+  auto info = comp.request();
+  if (cap < 0) throw std::invalid_argument("host_unlz4_block: cap < 0");
+  constexpr size_t kGuard = 32;
+  std::string out(static_cast<size_t>(cap) + 2 * kGuard, '\xA5');
+  std::unique_ptr<u64[]> win(
+      window ? new u64[tfrec::lz4::kWindowAlloc / 8] : nullptr);
+  i64 got = tfrec::lz4::unlz4_block(
+      static_cast<const u8*>(info.ptr),
+      static_cast<i64>(info.size * info.itemsize),
+      reinterpret_cast<u8*>(&out[kGuard]), cap, -1,
+      reinterpret_cast<u8*>(win.get()));
+  for (size_t i = 0; i < kGuard; ++i)
+    if (out[i] != '\xA5' || out[kGuard + cap + i] != '\xA5')
+      throw std::logic_error("unlz4_block wrote outside its output");
+  if (got < 0)
+    throw std::runtime_error("unlz4_block failed: cause " +
+                             std::to_string(-got));
+  return py::bytes(out.data() + kGuard, static_cast<size_t>(got));
+}
+
 // Host run of the raw-Snappy chunk compressor core shared with the gfx950
 // kernel (csrc/snappy_enc_core.h): `lane` < 0 emulates the lanes with loops
 // and is byte-identical to the device, which backs the CPU tests.
@@ -816,6 +843,7 @@ void register_deflate(py::module_& m);  // defined in csrc/hip/deflate.hip
 void register_inflate_foreign(py::module_& m);  // csrc/hip/inflate_foreign.hip
 void register_snappy(py::module_& m);   // defined in csrc/hip/snappy.hip
 void register_snappy_enc(py::module_& m);  // csrc/hip/snappy_enc.hip
+void register_lz4(py::module_& m);      // defined in csrc/hip/lz4.hip
 void register_collate(py::module_& m);  // defined in csrc/hip/collate.hip
 void register_stage_upload(py::module_& m);  // csrc/hip/stage_upload.hip
 
@@ -854,6 +882,11 @@ PYBIND11_MODULE(_native, m) {
         py::arg("expect_len"),
         "TEST-ONLY: run the device Snappy decoder's core on host for one raw "
         "chunk; raises RuntimeError naming the cause code on a refusal");
+  m.def("host_unlz4_block", &host_unlz4_block, py::arg("comp"),
+        py::arg("cap"), py::arg("window") = false,
+        "Decode one raw LZ4 block of at most `cap` bytes with the device "
+        "decoder's core on the host -> the bytes produced; raises "
+        "RuntimeError naming the cause code on a refusal");
   m.def("host_snap_chunk", &host_snap_chunk, py::arg("data"),
         "TEST-ONLY: run the device Snappy compressor's core on host for one "
         "block -> its raw chunk");
@@ -900,6 +933,7 @@ PYBIND11_MODULE(_native, m) {
   register_inflate_foreign(m);
   register_snappy(m);
   register_snappy_enc(m);
+  register_lz4(m);
   register_collate(m);
   register_stage_upload(m);
   m.attr("HAS_GPU_KERNELS") = true;

@@ -1555,6 +1555,15 @@ class SnappyRejected(DeviceDecompressRejected):
             paths, f"device snappy decode rejected {len(paths)} file(s)")
 
 
+class Lz4Rejected(DeviceDecompressRejected):
+    """The device LZ4 decoder refused a block of some `.lz4` files of a
+    group (`paths`); the caller reads those on the host."""
+
+    def __init__(self, paths):
+        super().__init__(
+            paths, f"device lz4 decode rejected {len(paths)} file(s)")
+
+
 # what the last foreign-gzip inflate did, per file: [(path, live chunks,
 # marker symbols, error word)] — read by the tests and bench_suite.py
 last_foreign: list = []
@@ -1802,9 +1811,123 @@ def _device_unsnap_group(data: torch.Tensor, items, device):
     return ok
 
 
+# what the last device LZ4 decode did, per file: [(path, blocks, error
+# word)] — read by the tests and bench_suite.py
+last_lz4: list = []
+
+# Largest container block the device takes, raw and compressed: one wave
+# walks one block's sequences serially (see SNAPPY_MAX_CHUNK_RAW). A file
+# with a longer block is read on the host.
+LZ4_MAX_BLOCK_RAW = 1 << 20
+
+
+def lz4_on_device() -> bool:
+    """TFREC_LZ4=device|host: where GPU-engine reads decompress `.lz4`
+    files (default device; host = the same decoder core on the CPU)."""
+    val = os.environ.get("TFREC_LZ4", "device").lower()
+    if val not in ("device", "host"):
+        raise ValueError(
+            f"Unsupported TFREC_LZ4 {val!r} (expected 'device' or 'host')")
+    return val == "device"
+
+
+def lz4_device_meta(path: str):
+    """(block extents, total raw size) of a `.lz4` file from its container
+    headers alone (io/paths.py lz4_walk over a read-only mmap, the bodies
+    stay untouched), or None when the file is not for the device decoder:
+    TFREC_LZ4=host, a container the walk marks host only, or a block above
+    LZ4_MAX_BLOCK_RAW. The extents are an int64 array of rows (in_off,
+    in_len, out_off, raw_len), one per block. Gates the device read path;
+    None sends the file to the host."""
+    import mmap
+
+    from ..io import paths as P
+
+    if not getattr(_native, "HAS_GPU_KERNELS", False) or not lz4_on_device():
+        return None
+    try:
+        size = os.path.getsize(path)
+        if size == 0:
+            return np.zeros((0, 4), np.int64), 0
+        with open(path, "rb") as f:
+            with mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as mm:
+                rows, total, device_ok = P.lz4_walk(mm, path)
+    except (OSError, ValueError):
+        return None
+    if not device_ok:
+        return None
+    ext = np.array(rows, np.int64).reshape(-1, 4)
+    if ext.shape[0] and int(ext[:, [1, 3]].max()) > LZ4_MAX_BLOCK_RAW:
+        return None
+    return ext, total
+
+
+def _lz4_max_waves(device) -> int:
+    """Grid cap of the LZ4 launch, in waves: what a CU keeps resident. The
+    kernel's registers allow 4 waves per SIMD (16 per CU, docs/KERNELS.md);
+    its LDS windows (LZ4_LDS_BYTES_PER_BLOCK per 4-wave workgroup of the
+    CU's 160 KiB) would allow more. More blocks than the cap take the
+    kernel's grid-stride loop."""
+    wg_per_cu = min(4, (160 << 10) // int(_native.LZ4_LDS_BYTES_PER_BLOCK))
+    return (int(_native.LZ4_WAVES_PER_BLOCK) * wg_per_cu *
+            torch.cuda.get_device_properties(device).multi_processor_count)
+
+
+def _device_unlz4_group(data: torch.Tensor, items, device):
+    """Decode several `.lz4` files in HBM in ONE launch, one container
+    block per wave (csrc/hip/lz4.hip), each file's bytes landing at
+    data[out_base : out_base + total]. items = [(path, lz4_device_meta,
+    out_base)]. As _device_unsnap_group: the compressed files DMA from the
+    page cache, the block table is checked against both buffers here before
+    it is uploaded, and the host waits once, for the per-file error words.
+    Returns one bool per item; False = a block was refused (the slice's
+    content is unspecified), read the file on the host."""
+    del last_lz4[:]
+    nfile = len(items)
+    comp, comp_offs, comp_sizes = _upload_group(items, device)
+    tables = []
+    block0 = np.zeros(nfile, np.int64)
+    nblock = 0
+    for k, (p, meta, out_base) in enumerate(items):
+        ext, total = meta
+        block0[k] = nblock
+        if ext.shape[0]:
+            t = np.empty((ext.shape[0], 5), np.int64)
+            t[:, 0] = ext[:, 0] + comp_offs[k]
+            t[:, 1] = ext[:, 1]
+            t[:, 2] = ext[:, 2] + out_base
+            t[:, 3] = ext[:, 3]
+            t[:, 4] = k
+            # every extent inside its own file's slice of both buffers
+            if (ext[:, 0].min() < 0 or ext[:, 1].min() < 0
+                    or (ext[:, 0] + ext[:, 1]).max() > comp_sizes[k]
+                    or ext[:, 2].min() < 0 or ext[:, 3].min() < 0
+                    or (ext[:, 2] + ext[:, 3]).max() > total
+                    or out_base < 0 or out_base + total > data.numel()):
+                raise ValueError(f"lz4 extents changed under the read: {p}")
+            tables.append(t)
+            nblock += ext.shape[0]
+    err = np.full(nfile, -1, np.int64)
+    if nblock:
+        assert int(_native.LZ4_BLOCK_COLS) == 5
+        bt_d = torch.as_tensor(np.concatenate(tables)).to(device)
+        b0_d = torch.as_tensor(block0).to(device)
+        err_d = torch.as_tensor(err).to(device)
+        _native.gpu_unlz4_blocks(
+            comp.data_ptr(), bt_d.data_ptr(), b0_d.data_ptr(), nblock,
+            data.data_ptr(), err_d.data_ptr(), _lz4_max_waves(device),
+            _stream())
+        err = err_d.cpu().numpy()  # the one host wait
+    ok = []
+    for k, (p, meta, _) in enumerate(items):
+        ok.append(int(err[k]) == -1)
+        last_lz4.append((p, int(meta[0].shape[0]), int(err[k])))
+    return ok
+
+
 class DeviceSource(NamedTuple):
     """Where a file's bytes come from when the device takes it."""
-    kind: str    # "raw" | "gzip" | "foreign" | "snappy"
+    kind: str    # "raw" | "gzip" | "foreign" | "snappy" | "lz4"
     meta: object  # what the kind's *_meta function returned; None for raw
     nbytes: int  # decompressed length
 
@@ -1826,13 +1949,18 @@ def _snappy_source(path: str) -> Optional[DeviceSource]:
     return None if meta is None else DeviceSource("snappy", meta, meta[1])
 
 
+def _lz4_source(path: str) -> Optional[DeviceSource]:
+    meta = lz4_device_meta(path)
+    return None if meta is None else DeviceSource("lz4", meta, meta[1])
+
+
 def device_source(path: str,
                   foreign_gzip: bool = False) -> Optional[DeviceSource]:
     """THE place that decides where a file's bytes come from: a raw DMA,
     the segment-table inflater (our gzip), the speculative inflater (any
     other writer's gzip, only with `foreign_gzip`, and only after the
-    segment table was looked for), the Snappy decoder, or, None, the host
-    codec. Every read path asks here, once per file, and hands the answer
+    segment table was looked for), the Snappy or the LZ4 decoder, or,
+    None, the host codec. Every read path asks here, once per file, and hands the answer
     on (read_files_to_batch `sources=`), so a file's header is walked once
     per read."""
     from ..io import paths as P
@@ -1845,6 +1973,8 @@ def device_source(path: str,
                                       else None)
     if codec == "snappy":
         return _snappy_source(path)
+    if codec == "lz4":
+        return _lz4_source(path)
     return None
 
 
@@ -1864,8 +1994,10 @@ def _source_image(path: str, src: Optional[DeviceSource], device,
         ok = _device_inflate_group(data, items, device)
     elif src.kind == "foreign":
         ok = _device_inflate_foreign_group(data, items, device, chunk_bytes)[0]
-    else:
+    elif src.kind == "snappy":
         ok = _device_unsnap_group(data, items, device)[0]
+    else:
+        ok = _device_unlz4_group(data, items, device)[0]
     return data if ok else None
 
 
@@ -1902,6 +2034,15 @@ def read_snappy_file_to_device(path: str,
     refused a chunk (callers fall back to the host codec)."""
     check_native()
     return _source_image(path, _snappy_source(path), device)
+
+
+def read_lz4_file_to_device(path: str,
+                            device="cuda") -> Optional[torch.Tensor]:
+    """`.lz4` file -> decompressed bytes in HBM via the device decoder.
+    None when the file is not eligible (lz4_device_meta) or the kernel
+    refused a block (callers fall back to the host codec)."""
+    check_native()
+    return _source_image(path, _lz4_source(path), device)
 
 
 def _deflate_max_waves(device) -> int:
@@ -2042,8 +2183,9 @@ def read_files_to_batch(paths, schema: StructType, record_type: str,
     Uncompressed files DMA straight from the page cache; gzip files bearing
     our segment table are inflated by the device inflater (all files'
     segments in one launch); `.snappy` files are decoded by the device
-    Snappy decoder (all files' chunks in one launch), and SnappyRejected
-    names those it refuses. With `foreign_gzip`, gzip files without the
+    Snappy decoder (all files' chunks in one launch), `.lz4` files by the
+    device LZ4 decoder (all files' blocks in one launch), and SnappyRejected
+    or Lz4Rejected names those they refuse. With `foreign_gzip`, gzip files without the
     table go through the speculative inflater into their own slices of the
     same image; if it refuses any, ForeignGzipRejected names them and
     nothing is decoded. `sources` hands over each path's device_source
@@ -2058,7 +2200,8 @@ def read_files_to_batch(paths, schema: StructType, record_type: str,
     for p, src in zip(paths, sources):
         if src is None:
             what = {"gzip": "gzip file without segment table",
-                    "snappy": "snappy file not for the device decoder"}
+                    "snappy": "snappy file not for the device decoder",
+                    "lz4": "lz4 file not for the device decoder"}
             raise ValueError(
                 f"{what.get(P.codec_from_path(p), 'file not for the device')}"
                 f": {p} (host path required)")
@@ -2077,7 +2220,7 @@ def read_files_to_batch(paths, schema: StructType, record_type: str,
     np.cumsum(sizes, out=bounds[1:])
     # each non-empty file with its slice of the image, bucketed by kind
     raw_files = []
-    items = {"gzip": [], "foreign": [], "snappy": []}
+    items = {"gzip": [], "foreign": [], "snappy": [], "lz4": []}
     for p, src, base in zip(paths, sources, bounds):
         if src.kind == "raw":
             raw_files.append((p, src.nbytes, int(base)))
@@ -2100,6 +2243,11 @@ def read_files_to_batch(paths, schema: StructType, record_type: str,
             # the host decoder decides what a refused file is: its bytes,
             # or an error that names the file
             raise SnappyRejected(refused)
+    if items["lz4"]:
+        ok = _device_unlz4_group(data, items["lz4"], device)
+        refused = [it[0] for it, good in zip(items["lz4"], ok) if not good]
+        if refused:
+            raise Lz4Rejected(refused)
     if gz_items and not _device_inflate_group(data, gz_items, device):
         # rare fallback: a segment the kernel rejected — host zlib fills
         # the affected files' slices

@@ -37,12 +37,15 @@ _CODEC_ALIASES = {
     "org.apache.hadoop.io.compress.defaultcodec": "deflate",
     "snappy": "snappy",
     "org.apache.hadoop.io.compress.snappycodec": "snappy",
+    "lz4": "lz4",
+    "org.apache.hadoop.io.compress.lz4codec": "lz4",
     "none": None,
     "uncompressed": None,
 }
 
-_EXTENSIONS = {"gzip": ".gz", "deflate": ".deflate", "snappy": ".snappy"}
-_EXT_TO_CODEC = {".gz": "gzip", ".deflate": "deflate", ".snappy": "snappy"}
+_EXTENSIONS = {"gzip": ".gz", "deflate": ".deflate", "snappy": ".snappy",
+               "lz4": ".lz4"}
+_EXT_TO_CODEC = {ext: codec for codec, ext in _EXTENSIONS.items()}
 
 
 class SaveModeError(RuntimeError):
@@ -165,6 +168,8 @@ def compress_bytes(data: bytes, codec: Optional[str]) -> bytes:
         return zlib.compress(data, 6)
     if codec == "snappy":
         return snappy_compress(data)
+    if codec == "lz4":
+        return lz4_compress(data)
     raise ValueError(codec)
 
 
@@ -309,6 +314,164 @@ def snappy_decompress(buf, name: str) -> bytes:
     return b"".join(parts)
 
 
+# ---------------------------------------------------------------------------
+# LZ4: the same Hadoop block container around raw LZ4 blocks
+# ---------------------------------------------------------------------------
+
+# Uncompressed bytes per block the writer emits. LZ4 offsets reach 64 KiB at
+# most, so larger blocks buy little ratio, and every block is one unit of
+# parallel work for the readers.
+_LZ4_BLOCK = int(os.environ.get("TFREC_LZ4_BLOCK", 64 << 10))
+
+
+def lz4_block_size() -> int:
+    if _LZ4_BLOCK <= 0 or _LZ4_BLOCK >= (1 << 31):
+        raise ValueError(
+            f"TFREC_LZ4_BLOCK must be in 1..2^31-1, got {_LZ4_BLOCK}")
+    return _LZ4_BLOCK
+
+
+def _lz4_raw():
+    import pyarrow as pa
+
+    return pa.Codec("lz4_raw")
+
+
+def lz4_pack_block(raw, codec=None) -> bytes:
+    """One container block holding `raw` (non-empty) as a single chunk."""
+    import struct as _struct
+
+    comp = (codec or _lz4_raw()).compress(raw, asbytes=True)
+    return _struct.pack(">II", len(raw), len(comp)) + comp
+
+
+def lz4_compress(data) -> bytes:
+    """Hadoop block container (layout: lz4_walk) of `data`, one chunk per
+    block of at most TFREC_LZ4_BLOCK raw bytes, compressed block by block
+    in the calling thread (see snappy_compress)."""
+    block = lz4_block_size()
+    codec = _lz4_raw()
+    view = memoryview(data)
+    return b"".join(lz4_pack_block(view[pos:pos + block], codec)
+                    for pos in range(0, len(view), block))
+
+
+def lz4_walk(buf, name: str):
+    """Walk the Hadoop block container of a `.lz4` file image by its headers.
+
+    THE LAYOUT is snappy_walk's (with its caveat: not yet checked against a
+    file that Hadoop wrote, see docs/PARITY.md): blocks of
+        u32 big-endian raw_len      uncompressed bytes the block holds
+    followed by one or more chunks, each
+        u32 big-endian comp_len     bytes that follow
+        comp_len bytes              one raw LZ4 block ("LZ4 Block Format")
+    and raw_len 0 or the end of the file ends the stream; an empty stream is
+    a zero-byte file. Our writer puts one chunk in every block; Hadoop
+    writes several when one write() exceeds its buffer.
+
+    Unlike a Snappy chunk, an LZ4 chunk does NOT state how many bytes it
+    produces. Only a block's raw_len is known from the headers, so where a
+    block ends in the file cannot be told from the headers alone when it
+    may hold several chunks: the u32 behind a chunk is either the next
+    block's raw_len or this block's next comp_len, and only decoding the
+    chunks (as Hadoop's reader does, and lz4_decompress here) settles it.
+    The walk therefore only hops over the headers and checks their extents
+    against the file. Behind each chunk it takes the u32 as the start of a
+    new block when a well-formed block header stands there (raw_len 0, or a
+    raw_len and a comp_len that fits the file) or the file ends there: the
+    single-chunk layout. Otherwise, when the u32 fits the file as a
+    comp_len, it takes it as a further chunk of the same block.
+
+    Returns (rows, total_raw, device_ok): one row per BLOCK, (in_off,
+    in_len, out_off, raw_len), where [in_off, in_off + in_len) spans all of
+    the block's chunks with their 4-byte headers. device_ok False marks the
+    file "host only": some position fits neither reading, or a header is
+    cut short; rows then holds what was walked before it. The split is a
+    guess wherever both readings fit, but a safe one: the device decoder
+    accepts a block only if its chunks produce exactly raw_len bytes from
+    exactly in_len, and a file it refuses is decoded by lz4_decompress,
+    which raises ValueError for a corrupt file."""
+    import struct as _struct
+
+    n = len(buf)
+    pos = 0
+    out_off = 0
+    rows = []
+    while pos < n:
+        if pos + 4 > n:
+            return rows, out_off, False
+        (raw_len,) = _struct.unpack_from(">I", buf, pos)
+        if raw_len == 0:
+            break
+        start = pos = pos + 4
+        while True:  # the block's chunks
+            if pos + 4 > n:
+                return rows, out_off, False
+            (comp_len,) = _struct.unpack_from(">I", buf, pos)
+            if comp_len == 0 or comp_len > n - pos - 4:
+                return rows, out_off, False
+            pos += 4 + comp_len
+            if pos == n:
+                break
+            if pos + 4 > n:
+                return rows, out_off, False
+            (nxt,) = _struct.unpack_from(">I", buf, pos)
+            if nxt == 0:
+                break
+            if pos + 8 <= n:
+                (c2,) = _struct.unpack_from(">I", buf, pos + 4)
+                if 0 < c2 <= n - pos - 8:
+                    break  # a well-formed block header
+        rows.append((start, pos - start, out_off, raw_len))
+        out_off += raw_len
+    return rows, out_off, True
+
+
+def lz4_decompress(buf, name: str) -> bytes:
+    """Uncompressed image of a `.lz4` file image (layout: lz4_walk), decoded
+    chunk by chunk in the calling thread: each chunk is given what its
+    block still misses as room and says how much it produced, which is
+    what finds the block's end (csrc/lz4_core.h through the native
+    module; the library's decoder wants the exact size up front)."""
+    import struct as _struct
+
+    from .. import _native
+
+    n = len(buf)
+    view = memoryview(buf)
+    pos = 0
+    block = 0
+    parts = []
+    while pos < n:
+        if pos + 4 > n:
+            raise ValueError(f"{name}: lz4 block {block}: truncated block "
+                             f"header at byte {pos}")
+        (left,) = _struct.unpack_from(">I", buf, pos)
+        pos += 4
+        if left == 0:
+            break
+        while left > 0:
+            if pos + 4 > n:
+                raise ValueError(f"{name}: lz4 block {block}: truncated "
+                                 f"chunk header at byte {pos}")
+            (comp_len,) = _struct.unpack_from(">I", buf, pos)
+            pos += 4
+            if comp_len > n - pos:
+                raise ValueError(
+                    f"{name}: lz4 block {block}: chunk of {comp_len} bytes "
+                    f"at byte {pos} runs past the end of the file")
+            try:
+                got = _native.host_unlz4_block(view[pos:pos + comp_len], left)
+            except RuntimeError as e:
+                raise ValueError(f"{name}: lz4 block {block}: chunk at byte "
+                                 f"{pos} is corrupt: {e}") from None
+            parts.append(got)
+            pos += comp_len
+            left -= len(got)
+        block += 1
+    return b"".join(parts)
+
+
 def parse_gz_segments(raw: bytes):
     """Parse our FEXTRA 'TS' segment table from a gzip blob.
 
@@ -449,6 +612,8 @@ def decompress_file(path: str) -> bytes:
         return zlib.decompress(raw)
     if codec == "snappy":
         return snappy_decompress(raw, path)
+    if codec == "lz4":
+        return lz4_decompress(raw, path)
     raise ValueError(codec)
 
 

@@ -293,7 +293,7 @@ def read_tfrecord(path: str, schema: Optional[StructType] = None,
                 except gpu_engine.DeviceDecompressRejected as rej:
                     # redo the group without the refused files: they take
                     # the host path, as with foreign_gzip="host" (gzip) or
-                    # TFREC_SNAPPY=host (snappy)
+                    # TFREC_SNAPPY=host (snappy), TFREC_LZ4=host (lz4)
                     import logging
 
                     for p in rej.paths:

@@ -15,8 +15,8 @@ outgrows the reserved table (`segment_table_capacity`), the table is
 dropped (padding only) and reads fall back to the full-flush marker scan,
 exactly like a foreign gzip file.
 
-snappy shards buffer raw bytes up to one container block (io/paths.py
-snappy_walk), emit each full block as it fills and the short tail on
+snappy and lz4 shards buffer raw bytes up to one container block (io/paths.py
+snappy_walk, lz4_walk), emit each full block as it fills and the short tail on
 close: the file is the one `write_tfrecord` writes for the same bytes.
 
     with ShardWriter(path + "/part-00000.tfrecord", schema) as w:
@@ -82,6 +82,13 @@ class ShardWriter:
             self._sn_buf = bytearray()
             self._sn_block = P.snappy_block_size()
             self._sn_codec = P._snappy_raw()
+            self._sn_pack = P.snappy_pack_block
+        elif self.codec == "lz4":
+            # the same container, cut into the LZ4 writer's blocks
+            self._sn_buf = bytearray()
+            self._sn_block = P.lz4_block_size()
+            self._sn_codec = P._lz4_raw()
+            self._sn_pack = P.lz4_pack_block
         self._closed = False
 
     # -- context manager --------------------------------------------------
@@ -143,7 +150,7 @@ class ShardWriter:
         self._f.write(extra)
         self._f.seek(0, os.SEEK_END)
 
-    # -- snappy block stream ------------------------------------------------
+    # -- snappy / lz4 block stream-------------------------------------------
     def _sn_append(self, raw: bytes, final: bool = False):
         """Buffer `raw`, emit every full block (the same blocks
         `compress_bytes` cuts), and the short tail when `final`."""
@@ -152,8 +159,8 @@ class ShardWriter:
         view = memoryview(self._sn_buf)
         pos = 0
         while len(view) - pos >= block or (final and pos < len(view)):
-            self._f.write(P.snappy_pack_block(view[pos:pos + block],
-                                              self._sn_codec))
+            self._f.write(self._sn_pack(view[pos:pos + block],
+                                        self._sn_codec))
             pos += block
         view.release()
         del self._sn_buf[:pos]
