@@ -5,7 +5,12 @@
 // exact sizes, so one byte read or written past either end trips the
 // sanitizer; each stream is walked serially, in place and through the staging
 // window, and once per lane (lane = 0..63, the device's share of the copies)
-// for the bounds of the lane-strided paths. Meant to be built with sanitizers
+// for the bounds of the lane-strided paths. The long streams (the edge cases
+// of tests/lz4_cases.py: a token, a literal's end or a bypassed literal at
+// every position around the window's edge, three refills, chunk runs) are
+// then mutated one byte at a time, 2000 mutants run for lanes -1, 0 and 63,
+// so malformed input also reaches a refill, a bypassed literal and a doubling
+// round; there only the bounds matter. Meant to be built with sanitizers
 // and run as its own executable on the CPU, before the kernel runs on a GPU:
 //
 //   clang++ -std=c++17 -O1 -g -fsanitize=address,undefined \
@@ -32,9 +37,11 @@ static Bytes rnd(size_t n) {  // xorshift32
   return b;
 }
 
-// Assembles a block sequence by sequence and plays it forward.
+// Assembles a block sequence by sequence and plays it forward; `hdr` lists
+// where its tokens, length bytes and offsets stand.
 struct Block {
   Bytes comp, out;
+  std::vector<size_t> hdr;
   static void ext(Bytes& c, size_t n) {
     if (n < 15) return;
     for (n -= 15; n >= 255; n -= 255) c.push_back(255);
@@ -42,14 +49,17 @@ struct Block {
   }
   // off < 0: the last sequence; `play` false leaves a bad match unplayed
   Block& seq(const Bytes& lit, int off = -1, size_t mlen = 4, bool play = true) {
-    size_t m = off < 0 ? 0 : mlen - 4;
+    size_t m = off < 0 ? 0 : mlen - 4, at = comp.size();
     comp.push_back((uint8_t)((lit.size() < 15 ? lit.size() : 15) << 4 | (m < 15 ? m : 15)));
     ext(comp, lit.size());
+    while (at < comp.size()) hdr.push_back(at++);
     comp.insert(comp.end(), lit.begin(), lit.end());
     out.insert(out.end(), lit.begin(), lit.end());
     if (off < 0) return *this;
+    at = comp.size();
     comp.push_back((uint8_t)off), comp.push_back((uint8_t)(off >> 8));
     ext(comp, m);
+    while (at < comp.size()) hdr.push_back(at++);
     for (size_t i = 0; play && i < mlen; ++i) out.push_back(out[out.size() - off]);
     return *this;
   }
@@ -105,13 +115,55 @@ static void check(const std::string& name, const Bytes& comp, int64_t cap,
   std::printf("ok   %s (%zu -> %lld)\n", name.c_str(), comp.size(), (long long)want_rc);
 }
 
+// The long valid streams, kept for the mutation loop at the end.
+struct Long {
+  std::string name;
+  Bytes comp;
+  int64_t cap;
+  bool chunked;
+  std::vector<size_t> hdr;  // of a raw block: its header bytes
+};
+static std::vector<Long> g_long;
+
 static void valid(const std::string& name, const Block& b) {
   check(name, b.comp, (int64_t)b.out.size(), (int64_t)b.out.size(), b.out);
   check(name + "+room", b.comp, (int64_t)b.out.size() + 77, (int64_t)b.out.size(), b.out);
+  // long in either sense: more input than a window, or (match_5000,
+  // match_70000) a match of many doubling rounds
+  if (b.comp.size() > 4000 || b.out.size() > 4000) g_long.push_back({name, b.comp, (int64_t)b.out.size(), false, b.hdr});
 }
 
 static void be32(Bytes& c, size_t v) {
   for (int s = 24; s >= 0; s -= 8) c.push_back((uint8_t)(v >> s));
+}
+
+// The chunk run of a container block, and what it produces.
+static Bytes chunks(std::initializer_list<const Block*> parts, Bytes* out) {
+  Bytes run;
+  for (const Block* c : parts) {
+    be32(run, c->comp.size());
+    run.insert(run.end(), c->comp.begin(), c->comp.end());
+    if (out) out->insert(out->end(), c->out.begin(), c->out.end());
+  }
+  return run;
+}
+
+// Sequences of exactly t bytes (4038..4292): the next token is byte t.
+static Block upto(size_t t) {
+  Block b;
+  b.seq(rnd(4000), 5, 4).seq(rnd(t - 4023), 5, 4);
+  if (b.comp.size() != t) std::printf("FAIL upto(%zu) is %zu bytes\n", t, b.comp.size()), ++g_fail;
+  return b;
+}
+
+// `n` short sequences: literals of 0..20 bytes, matches of 4..40 bytes.
+static Block& shorts(Block& b, int n) {
+  for (int k = 0; k < n; ++k) {
+    Bytes lit = rnd(rnd(1)[0] % 21 + (b.out.empty() ? 1 : 0));
+    size_t reach = b.out.size() + lit.size();
+    b.seq(lit, 1 + rnd(1)[0] % (reach < 200 ? reach : 200), 4 + rnd(1)[0] % 37);
+  }
+  return b;
 }
 
 int main() {
@@ -130,6 +182,36 @@ int main() {
       valid("window_" + std::to_string(t) + "_" + std::to_string(lit),
             Block().seq(rnd(4000), 5, 4).seq(rnd(t - 4023), 5, 4).seq(rnd(lit), 30, 8).tail());
   valid("literal_over_window", Block().seq(rnd(30), 3, 9).seq(rnd(5000), 4000, 70).seq(rnd(6), 1, 300).tail());
+  // the next token at stream byte t, then a literal and a match with length
+  // bytes: the window's edge in every part of a sequence in turn
+  for (size_t t = 4088; t <= 4100; ++t)
+    for (size_t lit : {0, 1, 3, 9, 15, 273}) {
+      Block b = upto(t);
+      b.seq(rnd(lit), 30, 300);
+      valid("token_at_" + std::to_string(t) + "_lit" + std::to_string(lit), shorts(b, 3).tail());
+    }
+  // a literal that ends inside the window, on its last byte (woff + n ==
+  // kWindow, the read of the slack words) and one past it (the bypass)
+  for (size_t end : {4095, 4096, 4097}) {
+    Block b;
+    b.seq(rnd(10), 3, 4).seq(rnd(end - 30), 77, 10);  // token, 16 length bytes
+    if (b.comp.size() != end + 2) std::printf("FAIL literal_ends_at_%zu layout\n", end), ++g_fail;
+    valid("literal_ends_at_" + std::to_string(end), shorts(b, 6).tail());
+  }
+  // bypassed literals: the window restarts behind them at every residue
+  for (size_t k = 0; k <= 8; ++k) {
+    Block b;
+    b.seq(rnd(5), 2, 4).seq(rnd(4096 + k), 100, 20);
+    valid("bypass_" + std::to_string(4096 + k), shorts(b, 12).tail());
+  }
+  {
+    Block b;
+    while (b.comp.size() < 3 * 4096 + 700) shorts(b, 50);
+    valid("three_refills", b.tail());
+    Block e = upto(4096 - 50);
+    e.seq(rnd(15 + 299 * 255 + 40), 65535, 300);  // 300 length bytes over the refill
+    valid("length_bytes_300", shorts(e, 5).tail());
+  }
   // one malformed block per cause
   const Bytes L = rnd(13);
   const int64_t N = 13 + 20 + 12;
@@ -156,6 +238,60 @@ int main() {
   Bytes past = three;
   past[0] = 0x7F;  // the first comp_len, far more than the block has
   check("chunk_past_block", past, (int64_t)all.size(), -lz4::LZ_CHUNK_PAST_BLOCK, {}, true);
+  g_long.push_back({"three_chunks", three, (int64_t)all.size(), true, {}});
+  // the causes again behind a window refill and doubling rounds
+  {
+    auto pre = [] { return Block().seq(rnd(3000), 5, 300).seq(rnd(1500), 70, 400); };
+    const int64_t P = (int64_t)pre().out.size(), M = P + N;
+    check("far:offset_zero", pre().seq(L, 0, 20, false).tail().comp, M, -lz4::LZ_OFFSET_ZERO, {});
+    check("far:offset_before_block", pre().seq(L, (int)P + 14, 20, false).tail().comp, M, -lz4::LZ_OFFSET_FAR, {});
+    Bytes c = pre().comp;
+    c.insert(c.end(), {0xF0, 0xFF, 0xFF});
+    check("far:length_bytes_cut", c, M, -lz4::LZ_LENGTH_PAST_INPUT, {});
+    c = pre().seq(L).comp, c.pop_back();
+    check("far:literal_cut", c, M, -lz4::LZ_LITERAL_PAST_INPUT, {});
+    check("far:output_overrun", pre().seq(L, 7, 30).tail().comp, M, -lz4::LZ_OUTPUT_OVERRUN, {});
+    check("far:match_overrun", pre().seq(L, 7, 70000).tail().comp, M, -lz4::LZ_OUTPUT_OVERRUN, {});
+    check("far:no_last_sequence", pre().seq(L, 7, 20).comp, M, -lz4::LZ_INPUT_SHORT, {});
+    c = pre().seq(L, 7, 8).comp, c.pop_back();
+    check("far:offset_cut", c, M, -lz4::LZ_INPUT_SHORT, {});
+    c = pre().seq(L, 7, 20).tail().comp, c.insert(c.end(), 3, 0);
+    check("far:input_left", c, M, -lz4::LZ_INPUT_LEFT, {});
+    // chunks: one that produces nothing, a small one behind a long one (the
+    // window still holds the long one's end), a header cut short, and a
+    // match that reaches into the previous chunk's output
+    Block big = pre().tail(), small = Block().seq(rnd(6), 2, 9).seq(rnd(3), 4, 5).tail(), none;
+    none.comp.push_back(0);
+    Bytes want, run = chunks({&b, &none, &a}, &want);
+    check("empty_chunk_in_the_middle", run, (int64_t)want.size(), (int64_t)want.size(), want, true);
+    want.clear(), run = chunks({&small, &big, &small}, &want);
+    check("small_big_small", run, (int64_t)want.size(), (int64_t)want.size(), want, true);
+    g_long.push_back({"small_big_small", run, (int64_t)want.size(), true, {}});
+    run = chunks({&a, &b}, nullptr), run.insert(run.end(), 3, 0);
+    check("chunk_header_cut", run, (int64_t)all.size(), -lz4::LZ_CHUNK_PAST_BLOCK, {}, true);
+    Block reach = Block().seq(rnd(5), 6, 8, false).tail();
+    check("match_into_previous_chunk", chunks({&big, &reach}, nullptr),
+          (int64_t)big.out.size() + 5 + 8 + 12, -lz4::LZ_OFFSET_FAR, {}, true);
+  }
+  // single-byte mutants of the long valid streams: only bounds matter. They
+  // are dealt round-robin, some 17 to a stream; every other round lands on a
+  // raw block's header bytes (a chunk run keeps no such list: its mutants
+  // fall anywhere, chunk headers included). Every third mutant gets spare
+  // room, so a lengthened match is copied, not refused.
+  {
+    size_t runs = 0;
+    for (int k = 0; k < 2000; ++k) {
+      const Long& s = g_long[k % g_long.size()];
+      Bytes m = s.comp;
+      Bytes r = rnd(5);
+      size_t at = ((size_t)r[0] << 16 | (size_t)r[1] << 8 | r[2]) % m.size();
+      // every other one on a token, a length byte or an offset
+      if ((k / g_long.size() & 1) && !s.hdr.empty()) at = s.hdr[at % s.hdr.size()];
+      m[at] ^= (uint8_t)(r[3] | 1);
+      for (int lane : {-1, 0, 63}) run(m, s.cap + (k % 3 ? 0 : 300), lane, true, s.chunked, nullptr), ++runs;
+    }
+    std::printf("ok   %zu mutant runs over %zu long streams\n", runs, g_long.size());
+  }
   // random byte soup under every cap: only bounds matter
   for (int k = 0; k < 3000; ++k) {
     Bytes soup = rnd(1 + k % 97);
